@@ -1,6 +1,14 @@
 """Throughput benchmark of the batched coverage env step (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5] [--envs B]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line.
+--full adds the legs that take runs of their own: today the CPU baseline (the
+oracle in --cpu-procs processes, ~2.5 s before the GPU is touched; the line's
+"cpu_baseline" is null without it).  --dump-outputs DIR writes what the last
+timed step left in the caller's output buffers (reward, done, obs; planes and
+dist for the SuperGridRL config) as DIR/<name>.npy after the timed region.
 
 One "step" = one launch of the HIP env kernel advancing every env of this
 GPU's shard by one timestep (all agents move, sense, merge, reward, done,
@@ -252,6 +260,41 @@ def measured_traffic(cfgname, warmup, steps):
                     "rocprofv3 kernel means of the same run)"}
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6  # --dump-outputs: all files of one run together
+
+
+def dump_outputs(dirpath, arrays, world, rank):
+    """--dump-outputs DIR: the caller's output buffers after the last timed
+    step as DIR/<name>.npy (DIR/<name>_rank<r>.npy for N > 1), float64 for the
+    float64 buffers and float32 for the others (uint8 and float32 convert
+    exactly).  `arrays` maps a name to a device tensor whose first axis is
+    the env.  A run whose outputs exceed DUMP_MAX_BYTES (over all ranks)
+    writes the same fixed, seeded sample of envs of every array, and the
+    sampled (shard-local) env indices as DIR/env_index.npy (float64, with
+    the same rank suffix).  Inputs are seeded
+    (shard_seeds), so two runs with the same arguments dump the same envs of
+    the same trajectories."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirpath, exist_ok=True)
+    out_dtype = {n: torch.float64 if t.dtype == torch.float64 else torch.float32 for n, t in arrays.items()}
+    B = next(iter(arrays.values())).shape[0]
+    per_env = sum(t[0].numel() * (8 if out_dtype[n] == torch.float64 else 4) for n, t in arrays.items()) + 8
+    budget = DUMP_MAX_BYTES // world - 1024 * (len(arrays) + 1)  # .npy headers
+    suffix = f"_rank{rank}" if world > 1 else ""
+    idx = None
+    if per_env * B > budget:
+        keep = max(1, budget // per_env)
+        host_idx = np.sort(np.random.RandomState(0).choice(B, size=keep, replace=False))
+        np.save(os.path.join(dirpath, f"env_index{suffix}.npy"), host_idx.astype(np.float64))
+        idx = torch.from_numpy(host_idx)
+    for name, t in arrays.items():
+        if idx is not None:
+            t = t.index_select(0, idx.to(t.device))
+        np.save(os.path.join(dirpath, f"{name}{suffix}.npy"), t.to(out_dtype[name]).cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -266,7 +309,14 @@ def main():
     # the whole machine): one single-env oracle process per core
     ap.add_argument("--cpu-procs", type=int, default=16)
     ap.add_argument("--cpu-secs", type=float, default=2.5)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline (the oracle in "
+                         "--cpu-procs processes for --cpu-secs, N = 1 only; \"cpu_baseline\" is null without it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the output buffers of the last timed step (reward, done, "
+                         "obs, ...) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (a fixed seeded "
+                         "sample of envs when they are larger)")
     ap.add_argument("--maxsteps", type=int, default=None,
                     help="episode length (auto-reset on done); default: the config's (1000, C5 2000)")
     ap.add_argument("--launch", default="native", choices=["native", "stream", "graph", "events"],
@@ -330,7 +380,7 @@ def main():
         return print_plan(args, world, rank, e0, e1, total_envs, scaling)
 
     cpu = None
-    if rank == 0 and world == 1 and args.gpus == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and args.gpus == 1 and not args.no_cpu:
         cpu = cpu_baseline(args.config, args.cpu_procs, args.cpu_secs)
 
     if args.sync == "spin":
@@ -396,6 +446,11 @@ def main():
                                native_call(env, a0 + astride, astride, K - 1, rp, dp, op, st)),
         events=args.events)
     env.check()
+    if args.dump_outputs:  # what the last timed step wrote into the buffers the launches were given
+        outs = {"reward": env.reward, "done": env.done, "obs": env.obs}
+        if env.dist_obs is not None:
+            outs["dist_obs"] = env.dist_obs
+        dump_outputs(args.dump_outputs, outs, world, rank)
     listed = dj_listed = served = dtot = None
     if dr:  # maps the last step sent to the full distance transform, and those the cache served (diagnostic)
         listed = int(env.get_state(marlcov._lib.FIELD_DIST_LISTED).item())
@@ -762,6 +817,9 @@ def bench_super(args, c, B, cpu, world, rank, dev, run):
     elapsed, step_ms, issue_us = timed_launches(lambda i, st: env.step_raw(actions[Wm + i].data_ptr(), rp, dp, st),
                                                 dev, K, launch)
     env.check()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"reward": env.reward, "done": env.done, "planes": env.planes,
+                                         "dist": env.dist}, world, rank)
     stats = torch.stack([env.reward.sum(), env.done.to(torch.float64).sum()])
     stats, elapsed = reduce_run(stats, elapsed, world)
     value = aggregate_rate(run["total_envs"], K, elapsed)

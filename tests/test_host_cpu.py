@@ -175,6 +175,40 @@ def test_c5_design_bytes_formula():
     assert f(8192, 16, 10, 2, 518, 100, 60, 40, 2) == 8192 * 15408 + extra / 2
 
 
+def test_bench_dump_outputs_exact_and_sampled(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float64 buffers stay float64, the others
+    become float32 with the same values; outputs above the byte limit are
+    the same seeded sample of envs in every array and in every run, named by
+    env_index.npy, and the files stay under the limit."""
+    import bench
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(5)
+    outs = {"reward": torch.rand(37, dtype=torch.float64, generator=g),
+            "done": torch.randint(0, 2, (37,), dtype=torch.uint8, generator=g),
+            "obs": torch.randint(0, 256, (37, 3, 2, 5, 5), dtype=torch.uint8, generator=g)}
+    bench.dump_outputs(str(tmp_path / "all"), outs, 1, 0)
+    assert sorted(os.listdir(tmp_path / "all")) == ["done.npy", "obs.npy", "reward.npy"]
+    for name, t in outs.items():
+        a = np.load(tmp_path / "all" / f"{name}.npy")
+        assert a.dtype == (np.float64 if name == "reward" else np.float32)
+        np.testing.assert_array_equal(a, t.numpy())
+    # 37 envs x (8 + 4 + 600 + 8) B = 22,940 B: a 12,000-B limit keeps a sample
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 12000)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), outs, 1, 0)
+    idx = np.load(tmp_path / "s1" / "env_index.npy")
+    assert idx.dtype == np.float64 and 1 <= len(idx) < 37 and np.all(np.diff(idx) > 0)
+    total = 0
+    for f in sorted(os.listdir(tmp_path / "s1")):
+        a = np.load(tmp_path / "s1" / f)
+        np.testing.assert_array_equal(a, np.load(tmp_path / "s2" / f))
+        if f != "env_index.npy":
+            np.testing.assert_array_equal(a, outs[f[:-4]].numpy()[idx.astype(np.int64)])
+        total += os.path.getsize(tmp_path / "s1" / f)
+    assert total <= 12000
+
+
 def test_tile_block_layout_round_trip():
     """marlcov.tiles mirrors the device map order (include/marlcov.h, ABI v3):
     4x4 blocks of 8x8-cell tiles, tile_index = ((ti/4)*TCS + tj/4)*16 +

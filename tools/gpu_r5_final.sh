@@ -16,7 +16,7 @@ b() {  # name, args...
   timeout -k 10 400 python3 bench.py "$@" > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.err" || { tail -5 "$OUT/bench_$n.err"; exit 1; }
   python3 -c "import json; d=json.load(open('$OUT/bench_$n.json')); r=d['roofline']; print('$n', round(d['value']/1e6,2), 'M', d['ms_per_step']*1e3, 'us/step', r['kernel_us'], 'kernel_us frac', r['frac'])"
 }
-b c2
+b c2 --full
 for i in 1 2 3; do b c2_short_$i --gpus 1 --steps 20 --warmup 5 --no-cpu; done
 b c4 --config c4 --steps 50 --warmup 5 --no-cpu
 b c5_steady --config c5 --steps 30 --warmup 600 --no-cpu

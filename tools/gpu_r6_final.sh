@@ -18,11 +18,11 @@ b() {  # name, args...
   python3 -c "import json; d=json.load(open('$OUT/bench_$n.json')); r=d['roofline']; c=d.get('cpu_baseline') or {}; print('$n', round(d['value']/1e6,2), 'M', d['ms_per_step']*1e3, 'us/step', r['kernel_us'], 'kernel_us frac', r['frac'], 'cpu', c.get('value'), c.get('reference_equiv_value'))"
 }
 if [ -z "${SKIP_BENCH:-}" ]; then
-b c2
+b c2 --full
 for i in 1 2 3; do b c2_short_$i --gpus 1 --steps 20 --warmup 5 --no-cpu; done
-b c4 --config c4 --steps 50 --warmup 5
+b c4 --config c4 --steps 50 --warmup 5 --full
 b c5_steady --config c5 --steps 30 --warmup 600 --no-cpu
-b c5 --config c5
+b c5 --config c5 --full
 b sg_c2 --config sg_c2 --no-cpu
 b c2_dijkstra --config c2_dijkstra --no-cpu
 b gpus2_gloo --gpus 2 --dist-backend gloo --steps 20 --warmup 5 --no-cpu

@@ -12,6 +12,6 @@ timeout -k 10 300 python3 bench.py --gpus 2 --dist-backend gloo --steps 20 --war
 rc=$?; echo "launcher rc=$rc"; cat "$OUT/bench_gpus2_gloo.json"; [ $rc -ne 0 ] && exit $rc
 timeout -k 10 120 python3 bench.py --gpus 2 --steps 5 --warmup 1 --no-cpu > "$OUT/bench_gpus2_rccl.json" 2> "$OUT/bench_gpus2_rccl.err"
 echo "rccl on one GPU rc=$? (expected non-zero)"; tail -2 "$OUT/bench_gpus2_rccl.err"
-timeout -k 10 300 python3 bench.py > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"
+timeout -k 10 300 python3 bench.py --full > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"
 rc=$?; echo "bench rc=$rc"; cat "$OUT/bench_c2.json"
 exit $rc

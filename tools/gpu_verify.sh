@@ -12,7 +12,7 @@ timeout -k 10 1200 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeou
 rc=$?; tail -3 "$OUT/gpu_tests.log"; [ $rc -ne 0 ] && exit $rc
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
 rc=$?; tail -2 "$OUT/smoke.log"; [ $rc -ne 0 ] && exit $rc
-timeout -k 10 300 python3 bench.py > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"
+timeout -k 10 300 python3 bench.py --full > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"
 rc=$?; echo "bench rc=$rc"; [ $rc -ne 0 ] && exit $rc
 cat "$OUT/bench_c2.json"
 [ -n "${NO_TRACE:-}" ] && exit 0
