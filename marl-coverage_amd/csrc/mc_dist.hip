@@ -83,10 +83,6 @@ constexpr int kInf = 1 << 20;                  // "no covered cell in this row"
 constexpr int kMaxRows = 832;                  // RX limit of the largest instantiation
 constexpr int kRowOff = 1024;                  // g - u + kRowOff > 0 (u < kMaxRows)
 constexpr int kMaxTrack = kDistStrips;         // strips whose max(d) the cache pass can skip by
-#ifndef MC_DIST_ONEPASS  // build knob (A/B): collect the cache cells in the transform pass
-#define MC_DIST_ONEPASS 1
-#endif
-constexpr bool kOnePass = MC_DIST_ONEPASS != 0;
 #ifndef MC_FAST_TILES  // build knob (A/B): tiles the cache fast path stages (box + 25 around the robot)
 // (1024 since round 5: 8 KB of LDS, more workgroups per CU; a box past it
 // sends the map to the full transform.  At the C5 steady state and early
@@ -546,7 +542,10 @@ __device__ __forceinline__ void cache_serve(const State& s, int T, uint32_t ea, 
 //      strips and publishes its best key, strip maxima, target cells and
 //      cache candidates (State::dist_g*); with S == 1 the one part
 //      finalises the map as mode 0 does
-//   3  the full list after mode 2 (S > 1): one workgroup per map merges the
+//   3  (no longer launched: since round 5 the part that arrives last at the
+//      map's counter, State::dist_pcnt, merges inside mode 2, the hand-off
+//      above; the kernel's mode-3 branches are still there)
+//      the full list after mode 2 (S > 1): one workgroup per map merges the
 //      parts' partials and finalises the map (the bitboard is staged only
 //      for a second cache pass).  A launch boundary orders the parts'
 //      stores before the merge: no per-map done counter, no device-scope
@@ -561,73 +560,9 @@ constexpr int kMaxParts = MC_MAX_PARTS;
 // (State::dist_gcand was [B][N][4 kDistK], 2 GB at C5).  Round 6: one
 // segment of kDistK per part ([kDistGSlots][kDistGParts][kDistK], 8 MB), so
 // a part publishes its count with a plain store instead of taking its
-// place with a returning atomic (MC_DIST_SEGS=0: one shared list of
-// 4 kDistK, places by atomicAdd)
+// place with a returning atomic
 static_assert(kDistGSlots == kSplitSlots / 2, "State::dist_gcand's slots");
 static_assert(kMaxParts <= kDistGParts, "State::dist_gcand's segments");
-#ifndef MC_DIST_SEGS
-#define MC_DIST_SEGS 1
-#endif
-constexpr bool kSegs = MC_DIST_SEGS != 0;
-constexpr int kGCand = 4 * kDistK;  // (kSegs = 0) candidates a split map's parts may publish
-#ifndef MC_DIST_FUSED  // build knob (A/B): 0 finalises split maps in a separate mode-3 launch
-#define MC_DIST_FUSED 1
-#endif
-// the part of a split map that finishes last finalises it inside mode 2
-// (`sc1` hand-off of the partials) instead of a mode-3 launch after it
-constexpr bool kFused = MC_DIST_FUSED != 0;
-#ifndef MC_DIST_XCD  // build knob (A/B): 1 keeps a split map's parts on one XCD
-// (tried, round 5: the transform launch took 59.0 vs 54.3 us per C5 steady
-// step with the parts spread over the XCDs, profiles/r5/xcd/)
-#define MC_DIST_XCD 0
-#endif
-constexpr bool kXcdParts = MC_DIST_XCD != 0;
-#ifndef MC_DIST_BALANCE  // build knob (A/B): 0 splits a map's strips evenly by count
-#define MC_DIST_BALANCE 1
-#endif
-constexpr bool kBalance = MC_DIST_BALANCE != 0;
-#ifndef MC_DIST_OPAQUE_TID  // build knob (A/B): 0 = round 5's item loop (VGPR spills at <17>)
-#define MC_DIST_OPAQUE_TID 1
-#endif
-#ifndef MC_DIST_ACQREL  // build knob (A/B): 0 = round 5's relaxed arrival add (ordering by vmcnt + sc1 only)
-#define MC_DIST_ACQREL 1
-#endif
-#ifndef MC_DIST_HO_SC1  // build knob (A/B): 0 = plain stores / loads for the hand-off (the acq_rel arrival orders them)
-#define MC_DIST_HO_SC1 1
-#endif
-#ifndef MC_DIST_SKIP_IDLE  // build knob (A/B): 1 = idle parts skip staging (measured slower, round 6)
-#define MC_DIST_SKIP_IDLE 0
-#endif
-// A part that the balanced split gives no running strip (fewer running
-// strips than parts) stages nothing: it only arrives, and stages the map
-// after all if it is the merger and the cache pass has to run.  Measured
-// slower (C5 steady 142.5 vs 140.3 us, default window 153.7 vs 151.6 us,
-// profiles/r6/hoab/): off
-constexpr bool kSkipIdle = MC_DIST_SKIP_IDLE != 0;
-#ifndef MC_DIST_STAGE1  // build knob (A/B): 0 keeps the two-pass staging (map rows, then extended rows)
-#define MC_DIST_STAGE1 1
-#endif
-constexpr bool kStage1 = MC_DIST_STAGE1 != 0;
-#ifndef MC_DIST_PARTLIST  // build knob (A/B): 1 = part lists (below); off: measured slower, round 6
-#define MC_DIST_PARTLIST 0
-#endif
-// Part lists: a split map without a cache bound (theta0 = 0, e.g. every map
-// early after a reset) -- each part collects its own cells with d >= its own
-// maximum - kDistT (a superset of its cells with d >= M - kDistT, M >= that
-// maximum) and publishes them like the one-pass candidates; a part whose
-// maximum is below the best published key - kDistT holds no cache cell and
-// skips it.  The merger then needs the serial cache pass only when a part
-// that overflowed its list reaches M - kDistT (State::dist_govf).
-// Measured slower (round 6, profiles/r6/dist/: C5 default window 162.5 vs
-// 158.0 us per step, steady 150.8 vs 147.0): the parts' extra strip passes
-// cost more than the merger's serial pass they save.  Kept as an A/B knob,
-// parity-tested (tests/test_gpu_shapes.py, 8 envs: the mass reset splits
-// every map with theta0 = 0).
-constexpr bool kPartList = MC_DIST_PARTLIST != 0 && kOnePass;
-// the split parts' hand-off words as agent-scope relaxed atomics (`sc1`),
-// or, under the acq_rel arrival, plain stores and loads (no faster within
-// the noise, profiles/r6/hoab/: kept sc1)
-constexpr bool kHoSc1 = MC_DIST_HO_SC1 != 0 || MC_DIST_ACQREL == 0;
 
 // The strips a full transform of map ea runs with the lower bound theta of
 // its new max(d) (bit st; the rest are pruned, dist_kernel_t's strip loop):
@@ -650,9 +585,6 @@ __device__ uint64_t strip_run_mask(const State& s, int pad, uint32_t ea, int the
   return m;
 }
 
-#ifndef MC_DIST_RELOAD  // build knob (A/B): 0 keeps one State for the whole kernel
-#define MC_DIST_RELOAD 1
-#endif
 // The State re-read from the kernel arguments at the item's phase boundaries
 // (as the env kernel's reload_state, mc_env_kernel.hip): the fields a phase
 // uses are loaded there instead of living in SGPRs -- spilled to VGPR lanes,
@@ -671,13 +603,11 @@ struct DistArgs {
   DistIO io;
 };
 __device__ __forceinline__ void dist_reload(State& s, DistIO& io) {
-  if constexpr (MC_DIST_RELOAD != 0) {
-    auto kp = __builtin_amdgcn_kernarg_segment_ptr();  // the DistArgs
-    asm volatile("" : "+s"(kp));
-    const DistArgs& A = *(const DistArgs*)kp;
-    s = A.s;
-    io = A.io;
-  }
+  auto kp = __builtin_amdgcn_kernarg_segment_ptr();  // the DistArgs
+  asm volatile("" : "+s"(kp));
+  const DistArgs& A = *(const DistArgs*)kp;
+  s = A.s;
+  io = A.io;
 }
 
 template <int kCL>
@@ -703,7 +633,6 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
   __shared__ int s_ccount;
   __shared__ int s_kept;
   __shared__ uint32_t s_base;
-  __shared__ int s_lb;
   __shared__ int s_smax[kMaxTrack];
   __shared__ int32_t s_ccell[kDistK];
   __shared__ uint16_t s_cdv[kDistK];  // d < 0xFFFF (the transform saturates there)
@@ -725,15 +654,10 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
   DSTAMP(tk);
   const uint32_t nF = mode >= 2 ? __atomic_load_n(full, __ATOMIC_RELAXED) : 0u;
   const int S = mode >= 2 && nF > 0 ? max(1, min(min(nstrips_all, kMaxParts), (int)(kSplitSlots / nF))) : 1;
-  // XCD-aware parts (mode 2, S > 1, a grid of whole XCD rounds): workgroup b
-  // runs on XCD b % 8, so item it = 8 l + x is part l % S of map
-  // 8 (l / S) + x -- every part of a map on one XCD, whose L2 then fetches
-  // the map's tiles once for all of them (each part stages the whole map)
-  const bool xcd = kXcdParts && mode == 2 && S > 1 && (gridDim.x & 7u) == 0u;
   ListView lv;
   lv.pre[kListShards] = 0;
   if (list && mode < 2) lv = list_view(s);
-  const uint32_t n_items = mode == 2   ? (xcd ? ((nF + 7u) >> 3) * 8u * (uint32_t)S : nF * (uint32_t)S)
+  const uint32_t n_items = mode == 2   ? nF * (uint32_t)S
                            : mode == 3 ? (S > 1 ? nF : 0u)
                                        : (list ? lv.pre[kListShards] : (uint32_t)gridDim.x);
   const bool strided = mode >= 2 || list != nullptr;
@@ -764,24 +688,19 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
     // per-thread address and lane mask of the item body out of the item loop
     // and keeps them live across it -- 24 VGPRs spilled to scratch (100 B per
     // lane, ~24 MB of scratch writes per C5 step) at <17>, none with this
-#if MC_DIST_OPAQUE_TID
     const int tid = opaque_tid();
-#else
-    const int tid = threadIdx.x;
-#endif
     dist_reload(s, io);
     // modes 2 / 3: the full-list entry (and mode 2's part)
-    const uint32_t l = it >> 3;
-    const uint32_t fi = mode == 2 ? (xcd ? (l / (uint32_t)S) * 8u + (it & 7u) : it / (uint32_t)S) : (mode == 3 ? it : 0u);
-    const int part = mode == 2 ? (xcd ? (int)(l % (uint32_t)S) : (int)(it - fi * (uint32_t)S)) : 0;
-    if (fi >= nF && mode == 2) continue;  // (xcd: this XCD's share ran out; uniform per workgroup)
+    const uint32_t fi = mode == 2 ? it / (uint32_t)S : (mode == 3 ? it : 0u);
+    const int part = mode == 2 ? (int)(it - fi * (uint32_t)S) : 0;
+    if (fi >= nF && mode == 2) continue;
     const uint32_t ea = mode >= 2 ? full[8 + 2 * fi] : (list ? list_entry(s, lv, list, it) : it);
     // the strips this workgroup transforms: a contiguous range, the ranges
     // splitting the map's running strips evenly (strip_run_mask; without a
     // mask, its strips)
     int st_lo = part * nstrips_all / S, st_hi = (part + 1) * nstrips_all / S;
-    bool idle = false;  // no running strip in this part's range (kSkipIdle)
-    if (kBalance && mode == 2 && S > 1 && s.dist_rmask) {
+    bool idle = false;  // (never set: the idle-part skip is gone; the flag leaves with the mode-3 branches)
+    if (mode == 2 && S > 1 && s.dist_rmask) {
       const uint64_t rm = s.dist_rmask[ea];
       if (rm) {
         const int R = __popcll(rm);
@@ -796,9 +715,6 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
         };
         st_lo = bound(part);
         st_hi = bound(part + 1);
-        const uint64_t upto_hi = st_hi >= 64 ? ~0ull : low_mask(st_hi);
-        const uint64_t upto_lo = st_lo >= 64 ? ~0ull : low_mask(st_lo);
-        idle = kSkipIdle && (rm & upto_hi & ~upto_lo) == 0ull;
       }
     }
     uint64_t ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, dflags = 0, tsa = 0, tsb = 0;
@@ -874,43 +790,38 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
       __syncthreads();  // the item's LDS scalars are initialised; every thread is past its own list
       if (tid == 0) s_ccount = 0;
       __syncthreads();
-      // the parts' candidates: a one-pass list (with theta0), the part lists
-      // (without), else none
-      const bool lists = (kOnePass && theta0 > 0) || kPartList;
-      // kSegs: part p's count and segment; pre[p] = the candidates before it
+      // the parts' candidates: a one-pass list (with theta0), else none
+      const bool lists = theta0 > 0;
+      // part p's count and segment; pre[p] = the candidates before it
       uint32_t pre[kMaxParts + 1];
       pre[0] = 0u;
       bool over = false;
 #pragma unroll
       for (int p = 0; p < kMaxParts; ++p) {
-        const uint32_t c = (kSegs && lists && p < S) ? ld_ho(s.dist_gcnt + (size_t)fi * kDistGParts + p, sc1) : 0u;
+        const uint32_t c = (lists && p < S) ? ld_ho(s.dist_gcnt + (size_t)fi * kDistGParts + p, sc1) : 0u;
         over |= c > (uint32_t)kDistK;
         pre[p + 1] = pre[p] + (c > (uint32_t)kDistK ? 0u : c);
       }
-      const uint32_t total = kSegs ? pre[kMaxParts] : (lists ? ld_ho(s.dist_gcnt + fi, sc1) : 0u);
+      const uint32_t total = pre[kMaxParts];
       const unsigned long long gk = ld_ho(s.dist_gkey + ea, sc1);
       const int thr = (int)(gk >> 48) - kDistT;  // the candidates that are cache cells
-      // a part list that overflowed and may hold cache cells: the serial pass
-      const uint32_t ovf = (kPartList && theta0 == 0) ? ld_ho(s.dist_govf + fi, sc1) : 0u;
       for (int t = tid; t < T; t += kDtThreads)
         s_d[t] = (int)(t < 5 ? ld_ho(pre_out + (size_t)ea * 8 + 1 + t, sc1)
                              : ld_ho(dist_obs + (size_t)ea * E * E + (t - 5), sc1));
       for (int st = tid; st < min(nstrips_all, kMaxTrack); st += kDtThreads)
         s_smax[st] = (int)ld_ho(s.dist_sm + (size_t)ea * kMaxTrack + st, sc1);
-      if (gk != 0 && (kSegs ? !over : total <= (uint32_t)kGCand))
+      if (gk != 0 && !over)
         for (int k = tid; k < (int)total; k += kDtThreads) {
-          size_t at = (size_t)fi * kGCand + k;
-          if constexpr (kSegs) {  // segment p holds candidates pre[p] .. pre[p + 1] - 1
-            uint32_t base = 0u;
-            int p = 0;
+          // segment p holds candidates pre[p] .. pre[p + 1] - 1
+          uint32_t base = 0u;
+          int p = 0;
 #pragma unroll
-            for (int q = 1; q < kMaxParts; ++q)
-              if ((uint32_t)k >= pre[q]) {
-                p = q;
-                base = pre[q];
-              }
-            at = ((size_t)fi * kDistGParts + p) * kDistK + ((uint32_t)k - base);
-          }
+          for (int q = 1; q < kMaxParts; ++q)
+            if ((uint32_t)k >= pre[q]) {
+              p = q;
+              base = pre[q];
+            }
+          const size_t at = ((size_t)fi * kDistGParts + p) * kDistK + ((uint32_t)k - base);
           const int2 c = ld_ho(s.dist_gcand + at, sc1);
           if (c.y >= thr) {
             const int j = atomicAdd(&s_ccount, 1);
@@ -924,22 +835,19 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
       if (tid == 0) {
         s_key = gk;
         s_cov = gk != 0;  // a covered map's key is nonzero (its far or cell field)
-        if (kSegs ? over : total > (uint32_t)kGCand) s_ccount = kDistK + 1;  // overflowed: the second pass
-        if (ovf > 0u && (int)ovf - 1 >= thr) s_ccount = kDistK + 1;
+        if (over) s_ccount = kDistK + 1;  // overflowed: the second pass
         s.dist_gkey[ea] = 0;  // zero for the map's next split transform
-        if (!kSegs) s.dist_gcnt[fi] = 0;
-        if (kPartList) s.dist_govf[fi] = 0;
       }
-      if (kSegs && tid < S) s.dist_gcnt[(size_t)fi * kDistGParts + tid] = 0;
+      if (tid < S) s.dist_gcnt[(size_t)fi * kDistGParts + tid] = 0;
       __syncthreads();
     };
     if (mode == 3) {
       merge_parts(false);
-      need_cb = s_cov && !(((kOnePass && theta0 > 0) || kPartList) && s_ccount <= kDistK);  // the second pass
+      need_cb = s_cov && !(theta0 > 0 && s_ccount <= kDistK);  // the second pass
     }
     // the map's row bitboard (Cb) in LDS
     auto stage_cb = [&]() {
-      if (kStage1 && pad <= 16) {
+      if (pad <= 16) {
         // one pass: a thread takes extended word w of one tile row (8 map
         // rows), loads the 8 tiles of map word w and the tile pair 8w-2,
         // 8w-1 (the last pad <= 16 columns of map word w-1, shifted in from
@@ -1374,7 +1282,7 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
       // (a bound below kDistT: every cell is a candidate, d >= 0 -- the list
       // then overflows and the cache pass runs; a negative threshold would
       // collect nothing and leave the list short)
-      strip(st, -1, (kOnePass && theta0 > 0) ? max(max(theta0, runmax) - kDistT, 0) : -1);
+      strip(st, -1, theta0 > 0 ? max(max(theta0, runmax) - kDistT, 0) : -1);
     }
     DSTAMP(ts2);
     dist_reload(s, io);
@@ -1398,82 +1306,41 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
       if (tid == 0 && s_key) atomicMax(s.dist_gkey + ea, s_key);
       for (int t = tid; t < T; t += kDtThreads)
         if (s_d[t] >= 0) {
-          if (t < 5) st_ho(pre_out + (size_t)ea * 8 + 1 + t, (float)s_d[t], kFused && kHoSc1);
-          else st_ho(dist_obs + (size_t)ea * E * E + (t - 5), (float)s_d[t], kFused && kHoSc1);
+          if (t < 5) st_ho(pre_out + (size_t)ea * 8 + 1 + t, (float)s_d[t], true);
+          else st_ho(dist_obs + (size_t)ea * E * E + (t - 5), (float)s_d[t], true);
         }
       for (int st = st_lo + tid; st < min(st_hi, kMaxTrack); st += kDtThreads)
-        if ((ran >> st) & 1ull) st_ho(s.dist_sm + (size_t)ea * kMaxTrack + st, (uint32_t)min(s_smax[st], 0xFFFF), kFused && kHoSc1);
-      bool part_list = false;  // this part collected its own candidates (theta0 = 0)
-      if (kPartList && theta0 == 0 && s.dist_ch) {
-        // the part's own maximum and the best key the parts published so far
-        // (a lower bound of M): below it by more than kDistT, no cache cell
-        if (tid == 0) {
-          const unsigned long long g = __hip_atomic_load((g_u64*)(s.dist_gkey + ea), __ATOMIC_RELAXED,
-                                                         __HIP_MEMORY_SCOPE_AGENT);
-          s_lb = (int)(max(g, (unsigned long long)s_key) >> 48);
-          s_ccount = 0;
-        }
-        __syncthreads();
-        const int pm = s_key ? (int)(s_key >> 48) : -1;
-        if (pm >= 0 && pm >= s_lb - kDistT) {
-          part_list = true;
-          const int thr = max(pm - kDistT, 0);
-          carry_in(st_lo);
-          for (int st = st_lo; st < st_hi; ++st) {
-            if (st >= kMaxTrack || s_smax[st] >= thr) {
-              strip(st, thr, -1);
-              __syncthreads();
-              if (s_ccount > kDistK) break;  // overflowed: the merger's pass if it matters
-            } else {
-              carry_over(st);
-            }
-          }
-          __syncthreads();
-          if (tid == 0 && s_ccount > kDistK) atomicMax(s.dist_govf + fi, (uint32_t)pm + 1u);
-        }
-      }
-      if ((kOnePass && theta0 > 0) || part_list) {
+        if ((ran >> st) & 1ull) st_ho(s.dist_sm + (size_t)ea * kMaxTrack + st, (uint32_t)min(s_smax[st], 0xFFFF), true);
+      if (theta0 > 0) {
         const int n = s_ccount;
-        if (n > 0 && (n <= kDistK || theta0 > 0)) {
-          if constexpr (kSegs) {  // this part's segment and count (kDistK + 1: overflowed)
-            const size_t sg = (size_t)fi * kDistGParts + part;
-            if (tid == 0) st_ho(s.dist_gcnt + sg, (uint32_t)min(n, kDistK + 1), kFused && kHoSc1);
-            if (n <= kDistK)
-              for (int k = tid; k < n; k += kDtThreads)
-                st_ho(s.dist_gcand + sg * kDistK + k, make_int2(s_ccell[k], s_cdv[k]), kFused && kHoSc1);
-          } else {
-            if (tid == 0) s_base = atomicAdd(s.dist_gcnt + fi, (uint32_t)(n <= kDistK ? n : kGCand + 1));
-            __syncthreads();
-            const uint32_t base = s_base;
-            if (n <= kDistK)
-              for (int k = tid; k < n; k += kDtThreads)
-                if (base + k < (uint32_t)kGCand)
-                  st_ho(s.dist_gcand + (size_t)fi * kGCand + base + k, make_int2(s_ccell[k], s_cdv[k]), kFused && kHoSc1);
-          }
+        if (n > 0) {
+          // this part's segment and count (kDistK + 1: overflowed)
+          const size_t sg = (size_t)fi * kDistGParts + part;
+          if (tid == 0) st_ho(s.dist_gcnt + sg, (uint32_t)min(n, kDistK + 1), true);
+          if (n <= kDistK)
+            for (int k = tid; k < n; k += kDtThreads)
+              st_ho(s.dist_gcand + sg * kDistK + k, make_int2(s_ccell[k], s_cdv[k]), true);
         }
       }
-      if constexpr (kFused) {
-        // every storing wave's stores done, then one arrival per part: an
-        // agent-scope acq_rel add (release: the part's published words are
-        // visible at agent scope before the count moves -- buffer_wbl2 of the
-        // XCD's L2 after the waves' stores have completed; acquire: the
-        // merger's loads after it miss its L1 / L2, buffer_inv).  The last
-        // to arrive merges (its other waves read after the barrier)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0)
-          s_base = MC_DIST_ACQREL ? __hip_atomic_fetch_add(s.dist_pcnt + ea, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT)
-                                  : atomicAdd(s.dist_pcnt + ea, 1u);
-        __syncthreads();
-        merged = s_base == (uint32_t)S - 1u;
-        if (merged && tid == 0)  // zero for the map's next split transform
-          __hip_atomic_store(s.dist_pcnt + ea, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      // every storing wave's stores done, then one arrival per part: an
+      // agent-scope acq_rel add (release: the part's published words are
+      // visible at agent scope before the count moves -- buffer_wbl2 of the
+      // XCD's L2 after the waves' stores have completed; acquire: the
+      // merger's loads after it miss its L1 / L2, buffer_inv).  The last
+      // to arrive merges (its other waves read after the barrier)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (tid == 0)
+        s_base = __hip_atomic_fetch_add(s.dist_pcnt + ea, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+      __syncthreads();
+      merged = s_base == (uint32_t)S - 1u;
+      if (merged && tid == 0)  // zero for the map's next split transform
+        __hip_atomic_store(s.dist_pcnt + ea, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (merged) {
         // the map's bitboard is staged here (every part stages it): a second
         // cache pass, if the parts' lists overflowed, needs no restaging
-        merge_parts(kHoSc1);
-        cov = s_cov != 0;  // the map's, from the parts' keys (an idle merger staged nothing)
+        merge_parts(true);
+        cov = s_cov != 0;  // the map's, from the parts' keys
       }
 #ifdef MC_DIST_STAMPS
       {  // a part (flag bit 52): stage, strips, publish (mode 3 leaves these)
@@ -1526,9 +1393,7 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
         // reaches it; the others only carry their last covered column)
         int cnt = -1;
         // the main pass's list (mode 3: the parts' lists) holds them all
-        // (mode 3 / a fused merger of a map without theta0: the part lists)
-        const bool parts = mode == 3 || (mode == 2 && S > 1);
-        const bool main_ok = kOnePass && (theta0 > 0 || (kPartList && parts)) && s_ccount <= kDistK;
+        const bool main_ok = theta0 > 0 && s_ccount <= kDistK;
         if (cov && M >= 0 && main_ok) {
           const int thr = M - kDistT, n = s_ccount;
           for (int k = tid; k < n; k += kDtThreads)
@@ -1541,7 +1406,7 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
           cnt = s_kept;
           dflags |= 1ull << 49;
         } else if (cov && M >= 0) {
-          if (idle) stage_cb();  // an idle part merging: the bitboard for the pass
+          if (idle) stage_cb();
           dflags |= 1ull << 50;
           __syncthreads();  // every thread has read s_ccount
           if (tid == 0) s_ccount = 0;
@@ -2183,8 +2048,8 @@ hipError_t launch_dist(const State& s, int pad, int post, float* pre_out, float*
 // (mc_env_kernel.hip dist_window) and lists only the maps with an unknown M
 // or a target the block cannot settle.  With the top-cell cache, the listed
 // maps first try the cache (mode 1) and the rest run split over workgroups
-// (mode 2; `full`: the full list), finalised by mode 3 when split over more
-// than one part; without it, each listed map runs whole (mode 0).  The grids
+// (mode 2; `full`: the full list), the part that finishes last finalising
+// its map; without it, each listed map runs whole (mode 0).  The grids
 // are fixed (hipGraph capture) and stride.
 // --------------------------------------------------------------------------
 hipError_t launch_dist_listed(const State& s, int pad, float* pre_out, float* dist_obs,
@@ -2202,9 +2067,7 @@ hipError_t launch_dist_listed(const State& s, int pad, float* pre_out, float* di
   // kSplitSlots items when it splits (a 2048-workgroup grid measured the
   // same: 202.3 vs 202.3 us per C5 steady step, profiles/r4/c5_grid/)
   const unsigned g2 = (unsigned)(maps < (size_t)kSplitSlots ? maps : (size_t)kSplitSlots);
-  e = launch_full(s, pad, 1, pre_out, dist_obs, nullptr, count, g2, 2, full, stream);
-  if (e != hipSuccess || kFused) return e;
-  return launch_full(s, pad, 1, pre_out, dist_obs, nullptr, count, g2 < 256 ? g2 : 256, 3, full, stream);
+  return launch_full(s, pad, 1, pre_out, dist_obs, nullptr, count, g2, 2, full, stream);
 }
 
 }  // namespace mc

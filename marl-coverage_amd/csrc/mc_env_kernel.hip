@@ -527,9 +527,6 @@ __device__ __forceinline__ void zero_marks(const State& s, const Ctx<NT, EPW, WT
 
 // tile (ti, tj) of agent a gathered from a row plane (the inverse scatter):
 // byte r of the tile = byte tj of word w0 + r * rs (row 8 ti + r; rs = N)
-#ifndef MC_GATHER_BYTES  // build knob (A/B): 0 extracts byte tj of 64-bit rows by shifts
-#define MC_GATHER_BYTES 1
-#endif
 template <typename WT>
 __device__ __forceinline__ uint64_t gather_tile(const WT* rows, int w0, int rs, int tj) {
   if constexpr (sizeof(WT) == 4) {
@@ -542,7 +539,7 @@ __device__ __forceinline__ uint64_t gather_tile(const WT* rows, int w0, int rs, 
     const uint32_t lo = __builtin_amdgcn_perm(h[1], h[0], 0x05040100u);
     const uint32_t hi = __builtin_amdgcn_perm(h[3], h[2], 0x05040100u);
     return (uint64_t)lo | ((uint64_t)hi << 32);
-  } else if constexpr (MC_GATHER_BYTES != 0) {
+  } else {
     // 64-bit rows: byte tj of the 8 rows by byte loads (the stage's scatter
     // writes them the same way), packed by v_perm -- instead of a 64-bit
     // shift, a mask and a 64-bit shift-or per row
@@ -558,11 +555,6 @@ __device__ __forceinline__ uint64_t gather_tile(const WT* rows, int w0, int rs, 
     const uint32_t lo = __builtin_amdgcn_perm(p23, p01, 0x05040100u);
     const uint32_t hi = __builtin_amdgcn_perm(p67, p45, 0x05040100u);
     return (uint64_t)lo | ((uint64_t)hi << 32);
-  } else {
-    uint64_t t = 0;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) t |= (uint64_t)((rows[w0 + r * rs] >> (8 * tj)) & (WT)0xFF) << (8 * r);
-    return t;
   }
 }
 
@@ -603,14 +595,8 @@ __device__ __forceinline__ void moves(const State& s, const Ctx<NT, EPW, WT>& C,
   if (C.sub == 0) { L.sc->pen = pen; L.sc->moved = moved; }
 }
 
-#ifndef MC_RPL_SHAPE  // A/B knob: 0 keeps 2 rays per lane per pass for every one-env-per-workgroup shape
-#define MC_RPL_SHAPE 1
-#endif
 #ifndef MC_ABL  // diagnostic ablations (timing only, results wrong): 1 no dist_window, 2 no dist rows in
 #define MC_ABL 0  // merge, 3 no overlap dedup in merge, 4 no obs, 5 no sensing march
-#endif
-#ifndef MC_MOVES_SERIAL  // A/B knob: 1 keeps the serial broadcast rounds (moves) at C5
-#define MC_MOVES_SERIAL 0
 #endif
 
 // Same moves for a compile-time agent count NS > 8 with one env per
@@ -1393,9 +1379,6 @@ __device__ __forceinline__ void dist_window(const State& s, const Ctx<NT, EPW, W
   }
 }
 
-#ifndef MC_DIST_AM  // build knob (A/B): 0 keeps the (agent, target) item loop for T <= 32
-#define MC_DIST_AM 1
-#endif
 // The same terms, agent-major, when the targets fit 32 lanes (T = 5 + E*E
 // <= 32, e.g. egoradius 2): lane l of the slot takes target l % 32 of agent
 // a0 + l / 32 in pass a0, so a lane's target offsets are computed once for
@@ -1447,9 +1430,6 @@ __device__ __forceinline__ void dist_window_am(const State& s, const Ctx<NT, EPW
   }
 }
 
-#ifndef MC_DIST_AM2  // build knob (A/B): 0 keeps dist_window_am's pass-by-pass loop
-#define MC_DIST_AM2 1
-#endif
 // dist_window_am with the agent count known at compile time (NS): the passes'
 // first row reads (the target's own row: the common answer) are issued
 // together, then the few lanes whose target is not covered scan outward,
@@ -1549,9 +1529,6 @@ __device__ __forceinline__ void store_tiles(const State& s, const Ctx<NT, EPW, W
   }
 }
 
-#ifndef MC_RELOAD  // build knob (A/B): 0 keeps one State for the whole kernel
-#define MC_RELOAD 1
-#endif
 // The kernel's State re-read at a phase boundary from the kernel arguments
 // through an opaque kernarg pointer: the fields the next phase uses are
 // loaded there (s_load, scalar cache) instead of staying live in SGPRs across
@@ -1577,7 +1554,7 @@ struct EnvArgs {
 };
 template <class SH, int EPW>
 __device__ __forceinline__ void reload_state(State& s, EnvIO& io) {
-  if constexpr (MC_RELOAD != 0 && EPW == 1) {
+  if constexpr (EPW == 1) {
     auto kp = __builtin_amdgcn_kernarg_segment_ptr();  // the EnvArgs
     asm volatile("" : "+s"(kp));
     const EnvArgs& A = *(const EnvArgs*)kp;
@@ -1586,46 +1563,20 @@ __device__ __forceinline__ void reload_state(State& s, EnvIO& io) {
     specialize<SH>(s);
   }
 }
-template <class SH, int EPW>
-__device__ __forceinline__ void reload_state(State& s) {
-  EnvIO io;
-  reload_state<SH, EPW>(s, io);
-}
-// (also inside sense_and_merge / reset_env: slower, C4 123.9 vs 123.2 us, C5
-// steady 137.0 vs 136.3 us, profiles/r6/rlab2/)
-#ifndef MC_RELOAD_INNER  // build knob (A/B): 1 = re-read inside sense_and_merge / reset_env too
-#define MC_RELOAD_INNER 0
-#endif
-#ifndef MC_UNIFORM_FLAGS  // build knob (A/B): 0 keeps the env flags as lane values
-#define MC_UNIFORM_FLAGS 1
-#endif
-template <class SH, int EPW>
-struct Reload {
-  __device__ __forceinline__ void operator()(State& s) const {
-    if constexpr (MC_RELOAD_INNER != 0) reload_state<SH, EPW>(s);
-  }
-};
-struct NoReload {
-  __device__ __forceinline__ void operator()(State&) const {}
-};
 
-// sense -> (lidar: gather) -> (single tool) -> merge, with the barriers (rl:
-// the State re-read between them, reload_state)
-template <int NT, int EPW, typename WT, int KI, int SUK, int NS, int KN, int KM = 0, int RPLX = 0,
-          class RL = NoReload>
+// sense -> (lidar: gather) -> (single tool) -> merge, with the barriers
+template <int NT, int EPW, typename WT, int KI, int SUK, int NS, int KN, int KM = 0, int RPLX = 0>
 __device__ __forceinline__ void sense_and_merge(const State& s0, const Ctx<NT, EPW, WT>& C,
-                                                Items<KI>& I, RL rl = RL()) {
+                                                Items<KI>& I) {
   State s = s0;
   if (MC_ABL != 5) sense<NT, EPW, WT, SUK, KN, KM, RPLX>(s, C);
   __syncthreads();
   STAMP(13);
-  rl(s);
   if (s.sensor == 0) {
     gather_marks<NT, EPW, WT, KI>(s, C, I);
     __syncthreads();
   }
   STAMP(4);
-  rl(s);
   if (s.sst) {
     single_tool<NT, EPW, WT>(s, C);
     __syncthreads();
@@ -1647,10 +1598,9 @@ __device__ __forceinline__ void set_agent(const State& s, const Lds<WT>& L, int 
   L.by[a] = (y - s.H - 1) >> 3;
 }
 
-template <int NT, int EPW, typename WT, int SUK, int NS, int KN, bool O32, int KM = 0, int RPLX = 0,
-          class RL = NoReload>
+template <int NT, int EPW, typename WT, int SUK, int NS, int KN, bool O32, int KM = 0, int RPLX = 0>
 __device__ __forceinline__ void reset_env(const State& s, const Ctx<NT, EPW, WT>& C,
-                                          const int32_t* inj_pos, RL rl = RL()) {
+                                          const int32_t* inj_pos) {
   constexpr int LPE = Ctx<NT, EPW, WT>::LPE;
   constexpr int KI = Ctx<NT, EPW, WT>::KI;
   const Lds<WT>& L = C.L;
@@ -1725,7 +1675,7 @@ __device__ __forceinline__ void reset_env(const State& s, const Ctx<NT, EPW, WT>
   zero_marks<NT, EPW, WT>(s, C);
   stage<NT, EPW, WT, KI, O32>(s, C, g, /*load_masks=*/false, I);
   __syncthreads();
-  sense_and_merge<NT, EPW, WT, KI, SUK, NS, KN, KM, RPLX>(s, C, I, rl);
+  sense_and_merge<NT, EPW, WT, KI, SUK, NS, KN, KM, RPLX>(s, C, I);
   store_tiles<NT, EPW, WT, KI, O32>(s, C, I);
   __syncthreads();
   if (C.sub == 0) {
@@ -1998,7 +1948,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
   constexpr int NSM = (SH::N > 0 && SH::N <= 8) ? SH::N : 0;  // compile-time agent count, if small
   // rays per lane per march pass: 3 where that saves a pass over the
   // default (C5: 336 rays over 128 lanes, one pass of 3 instead of two of 2)
-  constexpr int RPLK = MC_RPL_SHAPE && SH::N > 0 && SH::NB > 0 && SH::NB < 64 && EPW == 1 &&
+  constexpr int RPLK = SH::N > 0 && SH::NB > 0 && SH::NB < 64 && EPW == 1 &&
                                (SH::N * SH::NB + 3 * NT - 1) / (3 * NT) < (SH::N * SH::NB + CtxT::RPL * NT - 1) / (CtxT::RPL * NT)
                            ? 3
                            : 0;
@@ -2083,8 +2033,8 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
   const int act = is_step ? act_raw : 255;
   // one env per workgroup: the env's flags are uniform -- made scalar
   // (readfirstlane), their branches are scalar branches instead of lane masks
-  // kept in SGPR pairs (MC_UNIFORM_FLAGS)
-  auto uni = [](int v) { return (EPW == 1 && MC_UNIFORM_FLAGS) ? __builtin_amdgcn_readfirstlane(v) : v; };
+  // kept in SGPR pairs
+  auto uni = [](int v) { return EPW == 1 ? __builtin_amdgcn_readfirstlane(v) : v; };
   const int act0 = uni(is_step ? act0_raw : 0);  // agent 0's byte: the sentinel
   const int req = uni(io.env_mask != nullptr ? req_raw : 1);
 
@@ -2108,7 +2058,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
     L.sc->dist_hit = 0;
     L.sc->dist_fail = 0;
     L.sc->zero = 0;
-    if constexpr (EPW == 1 && MC_UNIFORM_FLAGS)
+    if constexpr (EPW == 1)
       L.sc->path = (active ? kPathActive : 0) | (reset_req ? kPathResetReq : 0) | (sent_reset ? kPathSentReset : 0) |
                    (sentinel ? kPathSentinel : 0);
   }
@@ -2188,7 +2138,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
       // per env kernel, profiles/r4/c5_grid/)
       if constexpr (SH::N > 0 && SH::N <= 8) {
         if (NT == 64 || C.sub < 64) moves_regs<NT, EPW, WT, SH::N>(s, C, -s.pen);
-      } else if constexpr (SH::N > 8 && EPW == 1 && !MC_MOVES_SERIAL) {
+      } else if constexpr (SH::N > 8 && EPW == 1) {
         if (C.sub < 64) moves_par<NT, EPW, WT, SH::N>(s, C, -s.pen);
       } else if (C.sub < 64) {
         moves<NT, EPW, WT>(s, C, -s.pen);
@@ -2209,7 +2159,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
     uint32_t free_old_r = free_old, vis_old_r = vis_old;
     int currstep_r = currstep0;
     double dthresh_r = dthresh0;
-    if constexpr (EPW == 1 && MC_UNIFORM_FLAGS) {
+    if constexpr (EPW == 1) {
       free_old_r = el<O32>(s.free_cnt, e);
       vis_old_r = el<O32>(s.vis_cnt, e);
       currstep_r = el<O32>(s.currstep, e);
@@ -2223,7 +2173,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
       dpre0 = pr[0];
       dprek = pr[1 + k];
     }
-    sense_and_merge<NT, EPW, WT, KI, SUK, NSM, SH::KN, SH::KM, RPLK>(s, C, I, Reload<SH, EPW>());
+    sense_and_merge<NT, EPW, WT, KI, SUK, NSM, SH::KN, SH::KM, RPLK>(s, C, I);
     __syncthreads();
     STAMP(5);
     reload_state<SH, EPW>(s, io);
@@ -2300,8 +2250,8 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
         // (tried, round 5: one lane per (agent, target row) growing the
         // row's covered set by a bit-parallel dilation -- 83.6 against 81.7
         // us at the C5 steady state, profiles/r5/win/; removed)
-        if constexpr (Ctx<NT, EPW, WT>::LPE % 32 == 0 && MC_DIST_AM) {
-          if constexpr (MC_DIST_AM2 && SH::N > 0 && SH::N <= 64) {
+        if constexpr (Ctx<NT, EPW, WT>::LPE % 32 == 0) {
+          if constexpr (SH::N > 0 && SH::N <= 64) {
             if (5 + s.E * s.E <= 32) dist_window_am2<NT, EPW, WT, SH::N>(s, C, skip);
             else dist_window<NT, EPW, WT>(s, C, skip);
           } else {
@@ -2324,7 +2274,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
       store_tiles<NT, EPW, WT, KI, O32>(s, C, I);
       STAMP(7);
     } else {
-      reset_env<NT, EPW, WT, SUK, NSM, SH::KN, O32, SH::KM, RPLK>(s, C, nullptr, Reload<SH, EPW>());  // the finished episode's tiles are not stored
+      reset_env<NT, EPW, WT, SUK, NSM, SH::KN, O32, SH::KM, RPLK>(s, C, nullptr);  // the finished episode's tiles are not stored
     }
   } else if (reset_req || sent_reset) {
     reload_state<SH, EPW>(s, io);
@@ -2334,7 +2284,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
       s.ep_pc[e] = (double)free_old / (double)s.numfree[g0];
       s.ep_len[e] = currstep0;
     }
-    reset_env<NT, EPW, WT, SUK, NSM, SH::KN, O32, SH::KM, RPLK>(s, C, reset_req ? io.inj_pos : nullptr, Reload<SH, EPW>());
+    reset_env<NT, EPW, WT, SUK, NSM, SH::KN, O32, SH::KM, RPLK>(s, C, reset_req ? io.inj_pos : nullptr);
     dlist = s.dist && C.sub < N;  // fresh maps: M unknown
   } else {
     // sentinel step without auto-reset / env left out of a partial reset:
@@ -2360,9 +2310,9 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
   __syncthreads();
 
   // the branch flags again, from LDS: one env per workgroup keeps them out of
-  // SGPR pairs across the branch (MC_UNIFORM_FLAGS)
+  // SGPR pairs across the branch
   const int path = L.sc->path;
-  constexpr bool kPathLds = EPW == 1 && MC_UNIFORM_FLAGS;
+  constexpr bool kPathLds = EPW == 1;
   const bool p_active = kPathLds ? (path & kPathActive) != 0 : active;
   const bool p_reset_req = kPathLds ? (path & kPathResetReq) != 0 : reset_req;
   const bool p_sent_reset = kPathLds ? (path & kPathSentReset) != 0 : sent_reset;
@@ -2487,10 +2437,6 @@ using ShapeC2B = Shape<4, 10, 21, 2, 10, 8, 3, 0, 0, 0, 0, 130>;
 using ShapeC5B = Shape<16, 10, 21, 2, 10, 8, 4, 1, 0, 0, 0, 514>;
 using ShapeC5 = Shape<16, 10, 21, 2, 10, 8, 4, 1>;  // 16 agents, egoradius 2, dist_reward (4 obs layers)
 
-#ifndef MC_BENCH_SHAPES  // build knob (A/B): 0 leaves the grid-baked bench instantiations out
-#define MC_BENCH_SHAPES 1
-#endif
-constexpr bool kBenchShapes = MC_BENCH_SHAPES != 0;
 
 #define MC_EL(T, P, W, SH, NAME) \
   EnvLaunch { "env_kernel<" #T "," #P "," NAME ">", &launch_one<T, P, W, SH> }
@@ -2505,7 +2451,7 @@ EnvLaunch select_env(const State& s, int nt, int epw) {
   const bool fits32 = (uint64_t)s.B * s.N * mtb < (1ull << 32) && (uint64_t)s.G * mtb < (1ull << 32);
   const bool spec = getenv_spec();
   if (epw == 2) {
-    if (narrow && fits32 && spec && kBenchShapes && ShapeC2B::matches(s)) return MC_EL(64, 2, uint32_t, ShapeC2B, "u32,C2");
+    if (narrow && fits32 && spec && ShapeC2B::matches(s)) return MC_EL(64, 2, uint32_t, ShapeC2B, "u32,C2");
     if (narrow && fits32 && spec && ShapeC2::matches(s)) return MC_EL(64, 2, uint32_t, ShapeC2, "u32,C2");
     if (narrow && fits32 && spec && ShapeC2D::matches(s)) return MC_EL(64, 2, uint32_t, ShapeC2D, "u32,C2D");
     if (narrow) return MC_EL(64, 2, uint32_t, Dynamic, "u32,generic");
@@ -2514,7 +2460,7 @@ EnvLaunch select_env(const State& s, int nt, int epw) {
   if (narrow) {
     if (nt == 64 && fits32 && spec && ShapeC2::matches(s)) return MC_EL(64, 1, uint32_t, ShapeC2, "u32,C2");
     if (nt == 64 && fits32 && spec && ShapeC2D::matches(s)) return MC_EL(64, 1, uint32_t, ShapeC2D, "u32,C2D");
-    if (nt == 128 && spec && kBenchShapes && ShapeC5B::matches(s)) return MC_EL(128, 1, uint32_t, ShapeC5B, "u32,C5");
+    if (nt == 128 && spec && ShapeC5B::matches(s)) return MC_EL(128, 1, uint32_t, ShapeC5B, "u32,C5");
     if (nt == 128 && spec && ShapeC5::matches(s)) return MC_EL(128, 1, uint32_t, ShapeC5, "u32,C5");
     switch (nt) {
       case 64: return MC_EL(64, 1, uint32_t, Dynamic, "u32,generic");
@@ -2524,7 +2470,7 @@ EnvLaunch select_env(const State& s, int nt, int epw) {
       default: return MC_EL(1024, 1, uint32_t, Dynamic, "u32,generic");
     }
   }
-  if (nt == 256 && fits32 && spec && kBenchShapes && ShapeC4B::matches(s)) return MC_EL(256, 1, uint64_t, ShapeC4B, "u64,C4");
+  if (nt == 256 && fits32 && spec && ShapeC4B::matches(s)) return MC_EL(256, 1, uint64_t, ShapeC4B, "u64,C4");
   if (nt == 256 && fits32 && spec && ShapeC4::matches(s)) return MC_EL(256, 1, uint64_t, ShapeC4, "u64,C4");
   if (nt == 256 && fits32 && spec && ShapeC4R::matches(s)) return MC_EL(256, 1, uint64_t, ShapeC4R, "u64,C4");
   switch (nt) {

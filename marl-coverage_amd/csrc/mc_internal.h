@@ -156,9 +156,8 @@ struct State {
   // published and its candidates [kDistGSlots][kDistGParts][kDistK] (cell, d)
   unsigned long long* dist_gkey;
   uint32_t* dist_gcnt;
-  // by full-list index: 1 + the largest own maximum of the parts whose
-  // candidate list overflowed (0: none), for maps split without a cache
-  // bound (theta0 = 0; mc_dist.hip part lists)
+  // (unused since the part lists left mc_dist.hip; kept until the kernel
+  // arguments' layout is next changed)
   uint32_t* dist_govf;
   int2* dist_gcand;
   uint32_t* dist_pcnt;  // [B][N] parts of a split map done this launch (mode 2 fused; zero between uses)
@@ -173,7 +172,7 @@ struct State {
 };
 
 constexpr int kMaxItemsPerLane = 2;  // staged (agent, tile) items per lane
-#ifndef MC_DIST_K  // build-time A/B knobs (tools/build_variants.py)
+#ifndef MC_DIST_K  // build-time tuning constants (tools/build_variants.py)
 #define MC_DIST_K 512
 #endif
 #ifndef MC_DIST_T

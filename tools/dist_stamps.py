@@ -70,7 +70,7 @@ def main():
     second = (s >> np.uint64(50)) & np.uint64(1)
     ph = [((s >> np.uint64(16 * i)) & np.uint64(0xFFFF)).astype(np.int64) * 16 for i in range(3)]
     ph.insert(0, (s >> np.uint64(51)).astype(np.int64) * 64)  # the fast-path attempt (part of stage)
-    part = (s >> np.uint64(52)) & np.uint64(1)  # a split map's part (mode 2; mode 3 does not stamp)
+    part = (s >> np.uint64(52)) & np.uint64(1)  # a split map's part (mode 2)
     fast = fast & (np.uint64(1) - part)
     for name, m in (("split part", part == 1), ("fast path", fast == 1), ("full, one-pass list", (fast == 0) & (kept == 1)),
                     ("full, second pass", (fast == 0) & (second == 1)),
