@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define MARLCOV_ABI_VERSION 9
+#define MARLCOV_ABI_VERSION 10
 
 enum {
   MC_OK = 0,
@@ -143,7 +143,8 @@ enum {
   MC_FIELD_EP_LEN = 17,      /* int32  [B] _currstep at the episode end        */
   /* dijkstra_input configs only (MC_EINVAL otherwise):                        */
   MC_FIELD_DJ_LISTED = 18,   /* int32 [1] (env, agent) paths the last step sent
-                                to the full-map BFS: nearest unexplored cell
+                                to the full-map BFS, LDS or HBM
+                                (mc_dijkstra_variant): nearest unexplored cell
                                 more than 24 steps away (read-only diagnostic) */
   /* dist_reward configs only:                                                 */
   MC_FIELD_DIST_CACHED = 19, /* int32 [1] of the maps the last POST listed, those
@@ -206,6 +207,17 @@ int mc_random_actions(void* env, uint64_t seed, int32_t step, uint8_t* dev_actio
  * of by rays.  Diagnostic: lets tests show which specialisation they cover.
  * The string stays valid until the calling thread's next call. */
 const char* mc_kernel_variant(void* env);
+
+/* Which kernels build the dijkstra_input layer: "window+lds" (the window
+ * kernel, then the full-map BFS with its bitboards in LDS for the paths
+ * longer than 24 steps), "window+hbm" (the same with the bitboards in a
+ * library-owned HBM scratch: maps whose bitboards exceed one workgroup's
+ * LDS, about 360 x 360 cells, or MARLCOV_DJ_BIG=1 at mc_create), "lds" /
+ * "hbm" (MARLCOV_DJ_FULL=1 at mc_create: every path on the full map), or ""
+ * without dijkstra_input.  The scratch has min(B * N, 256, 256 MiB / slot)
+ * slots (at least one; MARLCOV_DJ_BIG_GRID=1..4096 replaces the first 256), one per
+ * workgroup, and counts in mc_layout.state_bytes.  A static string. */
+const char* mc_dijkstra_variant(void* env);
 
 /* Which pool grid each env uses (int32 [B], device). */
 int mc_set_env_grids(void* env, const int32_t* dev_env_grid, void* stream);

@@ -11,7 +11,7 @@ import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libmarlcov.so")
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 MC_OK, MC_EINVAL, MC_EHIP, MC_ESTATE, MC_EDEVICE = 0, -1, -2, -3, -4
 SENSOR_LIDAR, SENSOR_SQUARE = 0, 1
@@ -135,6 +135,7 @@ SIGNATURES = [
     ("mc_set_env_grids", ctypes.c_int, [_VP, _VP, _VP]),
     ("mc_random_actions", ctypes.c_int, [_VP, _U64, _I32, _VP, _VP]),
     ("mc_kernel_variant", ctypes.c_char_p, [_VP]),
+    ("mc_dijkstra_variant", ctypes.c_char_p, [_VP]),
     ("mc_reset", ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
     ("mc_step", ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("mc_step_many", ctypes.c_int, [_VP, _VP, _I64, _I32, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _I64, _VP]),

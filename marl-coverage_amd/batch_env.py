@@ -321,6 +321,11 @@ class BatchCoverageEnv:
         """The env-kernel instantiation mc_step launches (mc_kernel_variant)."""
         return self.lib.mc_kernel_variant(self._h).decode()
 
+    def dijkstra_variant(self) -> str:
+        """The kernels of the dijkstra_input layer (mc_dijkstra_variant):
+        "window+lds", "window+hbm", "lds", "hbm", or "" without the layer."""
+        return self.lib.mc_dijkstra_variant(self._h).decode()
+
     def step_raw(self, actions_ptr: int, reward_ptr: int, done_ptr: int, obs_ptr: int, stream: int):
         """Zero-overhead launch for benchmarks: raw device pointers / stream."""
         return self.lib.mc_step(self._h, actions_ptr, reward_ptr, done_ptr, obs_ptr, None, stream)

@@ -27,7 +27,8 @@ hipError_t launch_gen(const State& s, uint64_t seed, double p, hipStream_t strea
 hipError_t launch_random_actions(const State& s, uint64_t seed, int step, uint8_t* out, hipStream_t stream);
 const char* env_variant(const State& s, int nt, int epw);
 hipError_t launch_dijkstra(const State& s, int pad, int layer, int Lc, uint8_t* obs,
-                           uint32_t* list, bool window, hipStream_t stream);
+                           uint32_t* list, bool window, uint64_t* big, unsigned big_slots,
+                           hipStream_t stream);
 hipError_t launch_dist(const State& s, int pad, int post, float* pre_out, float* dist_obs,
                        hipStream_t stream);
 hipError_t launch_dist_listed(const State& s, int pad, float* pre_out, float* dist_obs,
@@ -37,6 +38,8 @@ size_t dist_static_lds_bytes();
 int dist_max_rows();
 int dist_cache_max_rows();
 size_t dijkstra_lds_bytes(const State& s, int pad);
+size_t dijkstra_big_slot_bytes(const State& s, int pad);
+unsigned dijkstra_big_slots(const State& s, int pad);
 hipError_t launch_minimap(const State& s, int mini, double* out, hipStream_t stream);
 __global__ void dijkstra_kernel(State s, int pad, int layer, int Lc, uint8_t* obs_out,
                                 const uint32_t* list, uint32_t* count);
@@ -74,6 +77,8 @@ struct Env {
   size_t dj_lds = 0;  // dijkstra_input: LDS bytes of the BFS kernel
   uint32_t* dj_list = nullptr;  // dijkstra_input: count, done, last count + [B*N] items (full-map BFS)
   bool dj_window = true;        // dijkstra_input: window kernel first (MARLCOV_DJ_FULL=1: off)
+  uint64_t* dj_big = nullptr;   // dijkstra_input: the HBM kernel's plane scratch (null: the LDS kernel)
+  unsigned dj_big_slots = 0;    // ... its slots = the HBM kernel's workgroups
   size_t dt_lds = 0;  // dist_reward: LDS bytes of the distance kernel
   float* dist_pre = nullptr;  // dist_reward: [B][N][8] (library-owned)
   float* dist_obs = nullptr;  // dist_reward: caller's float32 [B][N][E][E]
@@ -356,17 +361,39 @@ int mc_create(const mc_config* cfg, int hip_device, void** out_env) {
   }
   set_launch_shape(E);
   if (c.dijkstra_input) {
-    // the BFS bitboards of one (env, agent) live in one workgroup's LDS
+    // the end point of a path is the int32 cell index u * RY + v of the extended grid
+    if (((int64_t)s.Wp + 2 * c.pad) * ((int64_t)s.Lp + 2 * c.pad) > INT32_MAX) {
+      mc_destroy(E);
+      return fail(MC_EINVAL, "dijkstra_input: the %dx%d grid's extended cells exceed a 32-bit index",
+                  c.width, c.length);
+    }
+    // the BFS bitboards of one (env, agent) live in one workgroup's LDS where
+    // they fit; else (or with MARLCOV_DJ_BIG=1: tests of the HBM kernel at
+    // small shapes) in an HBM scratch, a slot per workgroup of the HBM kernel
     const size_t need = mc::dijkstra_lds_bytes(s, c.pad);
     int maxlds = 0;
     if (hipDeviceGetAttribute(&maxlds, hipDeviceAttributeMaxSharedMemoryPerBlock, hip_device) !=
-            hipSuccess ||
-        need + 1024 > (size_t)maxlds) {
+        hipSuccess) {
       mc_destroy(E);
-      return fail(MC_EINVAL, "dijkstra_input: %zu B of LDS bitboards for a %dx%d grid exceed the "
-                  "device's %d B per workgroup", need, c.width, c.length, maxlds);
+      return fail(MC_EHIP, "dijkstra_input: cannot query the device's LDS per workgroup");
     }
-    E->dj_lds = need;
+    const char* fb = getenv("MARLCOV_DJ_BIG");
+    if (need + 1024 > (size_t)maxlds || (fb && atoi(fb) == 1)) {
+      const unsigned slots = mc::dijkstra_big_slots(s, c.pad);
+      const size_t bytes = (size_t)slots * mc::dijkstra_big_slot_bytes(s, c.pad);
+      void* bq = nullptr;
+      if (dev_alloc(E, &bq, bytes) != MC_OK) {
+        std::string msg = g_err;
+        mc_destroy(E);
+        return fail(MC_EHIP, "dijkstra_input: %zu B of scratch (%u slots) for a %dx%d grid: %s", bytes,
+                    slots, c.width, c.length, msg.c_str());
+      }
+      E->dj_big = (uint64_t*)bq;
+      E->dj_big_slots = slots;
+      total += bytes;
+    } else {
+      E->dj_lds = need;
+    }
     void* lq = nullptr;
     if (dev_alloc(E, &lq, ((size_t)s.B * s.N + 3) * 4) != MC_OK) {
       std::string msg = g_err;
@@ -865,6 +892,17 @@ const char* mc_kernel_variant(void* env) {
   return name.c_str();
 }
 
+const char* mc_dijkstra_variant(void* env) {
+  Env* E = as_env(env);
+  if (!E) {
+    fail(MC_EINVAL, "mc_dijkstra_variant: null env");
+    return "";
+  }
+  if (!E->cfg.dijkstra_input) return "";
+  if (E->dj_window) return E->dj_big ? "window+hbm" : "window+lds";
+  return E->dj_big ? "hbm" : "lds";
+}
+
 int mc_set_env_grids(void* env, const int32_t* dev_env_grid, void* stream) {
   Env* E = as_env(env);
   if (!E || !dev_env_grid) return fail(MC_EINVAL, "mc_set_env_grids: null argument");
@@ -886,7 +924,7 @@ static int dijkstra_layer(Env* E, void* dev_obs, hipStream_t st) {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mc::dijkstra_kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)E->dj_lds));
   HIP_TRY(mc::launch_dijkstra(E->s, E->cfg.pad, 3, E->s.Lc, (uint8_t*)dev_obs, E->dj_list,
-                              E->dj_window, st));
+                              E->dj_window, E->dj_big, E->dj_big_slots, st));
   return MC_OK;
 }
 

@@ -29,9 +29,20 @@
 // is kept (two bitboards): a neighbour of a cost-j cell has cost j-1, j or
 // j+1, and mod 3 tells them apart.  Four lanes test the four neighbours of
 // the walk in parallel; the first valid one in reference order wins.
+//
+// Big kernel (dijkstra_big_kernel): the full kernel's role on maps whose
+// seven bitboards do not fit one workgroup's LDS (about 360 x 360 cells and
+// up).  Same BFS, same end point, same walk back; the planes sit in a
+// library-owned HBM scratch, one slot per workgroup of a fixed grid, and the
+// agent's tiles are read from the state directly.  Layer j only holds cells
+// within L1 distance j of the start, so its sweep covers the band of rows
+// sx - j .. sx + j and the words of columns sy - j .. sy + j: the work grows
+// with d*^2, not with the map, and a plane word is initialised by the sweep
+// that first meets it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <cstdlib>
 
 #include "mc_bitboard.h"
@@ -402,22 +413,285 @@ __global__ __launch_bounds__(64) void dijkstra_window_kernel(State s, int pad, i
   }
 }
 
+// ---- big kernel: the planes in HBM -----------------------------------------
+namespace {
+
+// workgroups (= scratch slots) of the big kernel: one per CU (256 depth-120
+// items on bg2_1073x1073 took 3.19 / 1.68 / 1.02 ms at 64 / 128 / 256,
+// profiles/r7/dj_big)
+constexpr unsigned kDjBigGrid = 256;
+constexpr size_t kDjBigBudget = 256ull << 20;   // bytes of scratch the slots may take together
+constexpr int kDjBigPlanes = 7;                 // ob, tg, bl, m0, m1, f0, f1
+
+// the words BFS layer j can touch: rows ulo..uhi, words wlo..whi of each
+struct DjBand {
+  int ulo, uhi, wlo, whi;
+  __device__ __forceinline__ bool rows(int u) const { return u >= ulo && u <= uhi; }
+  __device__ __forceinline__ bool words(int w) const { return w >= wlo && w <= whi; }
+};
+
+__device__ __forceinline__ DjBand dj_band(int sx, int sy, int j, int RX, int RY) {
+  const int r = min(j, RX + RY);  // every cell is within L1 distance RX + RY
+  return {max(sx - r, 0), min(sx + r, RX - 1), max(sy - r, 0) >> 6, min(sy + r, RY - 1) >> 6};
+}
+
+}  // namespace
+
+// One (env, agent) on the whole map, planes in this workgroup's scratch slot;
+// every thread of the workgroup calls it.  The slot still holds the last
+// solve's words, so nothing is read that this solve has not written: the
+// bands are nested, a word outside band j - 1 counts as empty (no reached
+// cell can lie there), and the sweep of layer j writes every plane of a word
+// that enters the band with it.  The frontier planes need no such care past
+// band 0: layer j writes nxt over all of band j, which is all that layer
+// j + 1 reads of it.  Threads hand words to each other only across the
+// __syncthreads() that ends a layer (one workgroup owns the slot).
+__device__ __forceinline__ void dijkstra_big(const State& s, int pad, int layer, int Lc,
+                                             uint8_t* __restrict__ obs_out, int e, int a,
+                                             uint64_t* planes) {
+  __shared__ int s_end[3], s_any[3], s_tg0;  // per BFS layer j: slot j % 3; the start cell's target bit
+  __shared__ uint32_t s_crop[32];
+  const int tid = threadIdx.x;
+  const int RX = s.Wp + 2 * pad, RY = s.Lp + 2 * pad, RW = (RY + 63) >> 6;
+  const size_t NW = (size_t)RX * RW;
+  uint64_t* const ob = planes;
+  uint64_t* const tg = planes + NW;
+  uint64_t* const bl = planes + 2 * NW;
+  uint64_t* const m0 = planes + 3 * NW;
+  uint64_t* const m1 = planes + 4 * NW;
+  uint64_t* const f0 = planes + 5 * NW;
+  uint64_t* const f1 = planes + 6 * NW;
+  // the agent's maps (tiles) and start cell
+  const uint64_t* tf = s.freem + ((size_t)e * s.N + a) * s.MT;
+  const uint64_t* to = s.obstm + ((size_t)e * s.N + a) * s.MT;
+  const int sx = s.pos[((size_t)e * s.N + a) * 2] + pad;
+  const int sy = s.pos[((size_t)e * s.N + a) * 2 + 1] + pad;
+  const uint64_t last = (RY & 63) ? low_mask(RY & 63) : ~0ull;
+  if (tid < 32) s_crop[tid] = 0;
+  if (tid < 3) {
+    s_end[tid] = INT32_MAX;
+    s_any[tid] = 0;
+  }
+  if (tid == 0) {  // band 0: the start cell's word
+    const int w = sy >> 6;
+    const size_t i = (size_t)sx * RW + w;
+    const uint64_t f = row_word(s, tf, pad, sx, w), o = row_word(s, to, pad, sx, w);
+    const uint64_t in = (w == RW - 1) ? last : ~0ull;
+    const uint64_t t = ~(f ^ o) & in, sb = 1ull << (sy & 63);
+    ob[i] = o & ~f & in;
+    tg[i] = t;
+    bl[i] = sb;
+    f0[i] = sb;
+    m0[i] = 0;
+    m1[i] = 0;
+    s_tg0 = (int)((t >> (sy & 63)) & 1ull);
+  }
+  __syncthreads();
+
+  // ---- BFS by layers ------------------------------------------------------
+  int dstar = -1, end = -1;
+  DjBand fb = dj_band(sx, sy, 0, RX, RY);  // the band of the last layer swept
+  if (s_tg0) {
+    dstar = 0;  // the start cell itself is unexplored
+    end = sx * RY + sy;
+  } else {
+    uint64_t* cur = f0;
+    uint64_t* nxt = f1;
+    for (int j = 1; j <= RX * RY; ++j) {
+      // slot j % 3 collects layer j; slot (j+1) % 3 is reset for the next
+      // layer: every thread has read slot (j-2) % 3 before this layer began
+      const int par = j % 3, nxt_slot = (j + 1) % 3;
+      if (tid == 0) {
+        s_end[nxt_slot] = INT32_MAX;
+        s_any[nxt_slot] = 0;
+      }
+      const DjBand pb = fb;  // band j - 1: the words written so far
+      fb = dj_band(sx, sy, j, RX, RY);
+      const int bw = fb.whi - fb.wlo + 1, n = (fb.uhi - fb.ulo + 1) * bw;
+      int any = 0, best = INT32_MAX;
+      for (int k = tid; k < n; k += kDjThreads) {
+        const int ur = k / bw, u = fb.ulo + ur, w = fb.wlo + (k - ur * bw);
+        const size_t i = (size_t)u * RW + w;
+        const bool old = pb.rows(u) && pb.words(w);
+        uint64_t d = 0;
+        if (pb.rows(u)) {
+          if (old) {
+            const uint64_t c = cur[i];
+            d = c | (c << 1) | (c >> 1);
+          }
+          if (pb.words(w - 1)) d |= cur[i - 1] >> 63;
+          if (pb.words(w + 1)) d |= cur[i + 1] << 63;
+        }
+        if (pb.words(w)) {
+          if (pb.rows(u - 1)) d |= cur[i - RW];
+          if (pb.rows(u + 1)) d |= cur[i + RW];
+        }
+        const uint64_t in = (w == RW - 1) ? last : ~0ull;
+        uint64_t o, r, t = 0;
+        if (old) {
+          o = ob[i];
+          r = bl[i];
+        } else {  // the word enters the band: g = free - obst, as dijkstra_full
+          const uint64_t f = row_word(s, tf, pad, u, w);
+          o = row_word(s, to, pad, u, w);
+          t = ~(f ^ o) & in;
+          o = o & ~f & in;
+          r = 0;
+          ob[i] = o;
+          tg[i] = t;
+        }
+        const uint64_t nf = d & ~r & ~o & in;
+        const int m = j % 3;
+        nxt[i] = nf;
+        if (!old) {
+          bl[i] = nf;
+          m0[i] = m == 1 ? nf : 0ull;
+          m1[i] = m == 2 ? nf : 0ull;
+        } else if (nf) {
+          bl[i] = r | nf;
+          if (m == 1) m0[i] |= nf;
+          if (m == 2) m1[i] |= nf;
+        }
+        if (nf) {
+          any = 1;
+          const uint64_t hit = nf & (old ? tg[i] : t);
+          if (hit) best = min(best, u * RY + 64 * w + __ffsll((unsigned long long)hit) - 1);
+        }
+      }
+      if (any) atomicOr(&s_any[par], 1);
+      if (best != INT32_MAX) atomicMin(&s_end[par], best);
+      __syncthreads();
+      if (s_end[par] != INT32_MAX) {
+        dstar = j;
+        end = s_end[par];
+        break;
+      }
+      if (!s_any[par]) break;  // no reachable unexplored cell: empty path
+      uint64_t* t = cur;
+      cur = nxt;
+      nxt = t;
+    }
+  }
+
+  // ---- walk back from the end point (first wave, lanes 0..3): the planes of
+  // the four neighbours from HBM, one dependent load per path cell; a
+  // neighbour outside the last band was never reached
+  const int E = s.E, ego = s.ego;
+  const int cx0 = sx - ego, cy0 = sy - ego;  // crop origin (dgrid coordinates)
+  if (dstar >= 0 && tid < 64) {
+    int cu = end / RY, cv = end - (end / RY) * RY;
+    int j = dstar;
+    const int du = tid == 0 ? 1 : (tid == 1 ? -1 : 0);
+    const int dv = tid == 2 ? 1 : (tid == 3 ? -1 : 0);
+    for (;;) {
+      if (tid == 0) {
+        const int r = cu - cx0, c = cv - cy0;
+        if (r >= 0 && r < E && c >= 0 && c < E) s_crop[r] |= 1u << c;
+      }
+      if (j == 0) break;
+      const int nu = cu + du, nv = cv + dv;
+      bool ok = false;
+      if (tid < 4 && nv >= 0 && nv < RY && fb.rows(nu) && fb.words(nv >> 6)) {
+        const size_t i = (size_t)nu * RW + (nv >> 6);
+        const int b = nv & 63;
+        const int m = (int)((m0[i] >> b) & 1ull) + 2 * (int)((m1[i] >> b) & 1ull);
+        ok = ((bl[i] >> b) & 1ull) && m == (j - 1) % 3;
+      }
+      const uint64_t v = __ballot(ok) & 0xFull;
+      if (!v) {  // cannot happen: a cost-j cell has a cost-(j-1) neighbour
+        if (tid == 0) atomicOr(s.err, ERR_WINDOW);
+        break;
+      }
+      const int q = __ffsll((unsigned long long)v) - 1;
+      cu = __shfl(nu, q);
+      cv = __shfl(nv, q);
+      --j;
+    }
+  }
+  __syncthreads();
+  // ---- obs layer `layer` of agent a: the path cells inside the crop ----------
+  uint8_t* dst = obs_out + (((size_t)e * s.N + a) * Lc + layer) * E * E;
+  for (int i = tid; i < E * E; i += kDjThreads) {
+    const int r = i / E, c = i - r * E;
+    dst[i] = (uint8_t)((s_crop[r] >> c) & 1u);
+  }
+}
+
+// dijkstra_kernel's role and list protocol (count[0..2] as there) with the
+// planes in HBM: workgroup blockIdx.x owns scratch slot blockIdx.x and strides
+// over the listed items (list == nullptr: over all n_all (env, agent) items).
+__global__ __launch_bounds__(kDjThreads) void dijkstra_big_kernel(State s, int pad, int layer, int Lc,
+                                                                  uint8_t* __restrict__ obs_out,
+                                                                  const uint32_t* __restrict__ list,
+                                                                  uint32_t* __restrict__ count,
+                                                                  uint32_t n_all, uint64_t* scratch,
+                                                                  size_t slot_words) {
+  uint64_t* planes = scratch + (size_t)blockIdx.x * slot_words;
+  const uint32_t n_items = list ? __atomic_load_n(count, __ATOMIC_RELAXED) : n_all;
+  for (uint32_t it = blockIdx.x; it < n_items; it += gridDim.x) {
+    __syncthreads();  // the previous item's reads (LDS and slot) are done
+    const uint32_t ea = list ? list[it] : it;
+    dijkstra_big(s, pad, layer, Lc, obs_out, (int)(ea / (uint32_t)s.N), (int)(ea % (uint32_t)s.N),
+                 planes);
+  }
+  if (list && threadIdx.x == 0) {
+    if (n_items == 0) {  // nothing listed: nothing to reset (every workgroup read 0)
+      if (blockIdx.x == 0) count[2] = 0;
+    } else {
+      __threadfence();
+      if (atomicAdd(count + 1, 1u) == gridDim.x - 1) {
+        atomicExch(count + 2, atomicExch(count, 0u));
+        atomicExch(count + 1, 0u);
+      }
+    }
+  }
+}
+
 size_t dijkstra_lds_bytes(const State& s, int pad) {
   const size_t RX = s.Wp + 2 * pad, RW = (s.Lp + 2 * pad + 63) / 64;
   return (7 * RX * RW + 2 * (size_t)s.MT) * 8;
 }
 
+// bytes of one scratch slot of the big kernel: its seven planes
+size_t dijkstra_big_slot_bytes(const State& s, int pad) {
+  const size_t RX = s.Wp + 2 * pad, RW = (s.Lp + 2 * pad + 63) / 64;
+  return kDjBigPlanes * RX * RW * 8;
+}
+
+// slots (= workgroups) of the big kernel: one per item up to the fixed grid
+// (MARLCOV_DJ_BIG_GRID: tests make many items share few slots) and to what
+// the scratch budget holds, at least one
+unsigned dijkstra_big_slots(const State& s, int pad) {
+  const char* v = getenv("MARLCOV_DJ_BIG_GRID");
+  const int g = v ? atoi(v) : 0;
+  size_t n = g > 0 && g <= 4096 ? (size_t)g : kDjBigGrid;
+  n = std::min(n, (size_t)s.B * s.N);
+  n = std::min(n, kDjBigBudget / dijkstra_big_slot_bytes(s, pad));
+  return (unsigned)std::max<size_t>(n, 1);
+}
+
 // list: u32 [3 + B*N] (entry count, workgroups done, last entry count, then
 // the entries),
 // library-owned, zero between steps.  window = false: every (env, agent) on
-// the full map (the parity tests' second mode).
+// the full map (the parity tests' second mode).  big: the big kernel's scratch
+// of big_slots slots (mc_create: the LDS bitboards do not fit, or
+// MARLCOV_DJ_BIG=1) -- it then takes the full kernel's place; nullptr: the
+// full kernel.
 hipError_t launch_dijkstra(const State& s, int pad, int layer, int Lc, uint8_t* obs,
-                           uint32_t* list, bool window, hipStream_t stream) {
-  const size_t lds = dijkstra_lds_bytes(s, pad);
+                           uint32_t* list, bool window, uint64_t* big, unsigned big_slots,
+                           hipStream_t stream) {
   const unsigned items = (unsigned)((size_t)s.B * s.N);
+  // dynamic LDS of the full kernel / words of a scratch slot of the big kernel
+  const size_t lds = big ? 0 : dijkstra_lds_bytes(s, pad);
+  const size_t slot_words = big ? dijkstra_big_slot_bytes(s, pad) / 8 : 0;
   if (!window) {
-    hipLaunchKernelGGL(dijkstra_kernel, dim3(items), dim3(kDjThreads), lds, stream, s, pad, layer,
-                       Lc, obs, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+    if (big)  // a fixed grid over every item: a slot per workgroup
+      hipLaunchKernelGGL(dijkstra_big_kernel, dim3(big_slots), dim3(kDjThreads), 0, stream, s, pad,
+                         layer, Lc, obs, (const uint32_t*)nullptr, (uint32_t*)nullptr, items, big,
+                         slot_words);
+    else
+      hipLaunchKernelGGL(dijkstra_kernel, dim3(items), dim3(kDjThreads), lds, stream, s, pad, layer,
+                         Lc, obs, (const uint32_t*)nullptr, (uint32_t*)nullptr);
     return hipGetLastError();
   }
   static const int depth = [] {  // MARLCOV_DJ_DEPTH: fewer exact layers (diagnostics, A/B)
@@ -427,6 +701,11 @@ hipError_t launch_dijkstra(const State& s, int pad, int layer, int Lc, uint8_t* 
   }();
   hipLaunchKernelGGL(dijkstra_window_kernel, dim3(items), dim3(64), 0, stream, s, pad, layer, Lc,
                      obs, list + 3, list, depth);
+  if (big) {  // the listed items: the big kernel's fixed grid strides over the count
+    hipLaunchKernelGGL(dijkstra_big_kernel, dim3(big_slots), dim3(kDjThreads), 0, stream, s, pad,
+                       layer, Lc, obs, (const uint32_t*)(list + 3), list, items, big, slot_words);
+    return hipGetLastError();
+  }
   // the listed items: a fixed grid (hipGraph capture) strides over the count
   static const unsigned full_grid = [] {  // MARLCOV_DJ_FULL_GRID: A/B of the fixed grid
     const char* v = getenv("MARLCOV_DJ_FULL_GRID");
