@@ -22,6 +22,7 @@ hipError_t launch_env(const State& s, int mode, const uint8_t* actions, const ui
                       uint8_t* adj, int nt, int epw, hipStream_t stream);
 int env_pack(const State& s);
 hipError_t launch_share(const State& s, const uint8_t* actions, hipStream_t stream);
+hipError_t launch_rec_field(const State& s, int off, int width, void* buf, bool to_rec, hipStream_t stream);
 hipError_t launch_pack(const State& s, const int8_t* grids, hipStream_t stream);
 hipError_t launch_gen(const State& s, uint64_t seed, double p, hipStream_t stream);
 hipError_t launch_random_actions(const State& s, uint64_t seed, int step, uint8_t* out, hipStream_t stream);
@@ -99,23 +100,37 @@ struct Env {
 struct FieldDesc {
   void* ptr;
   int64_t bytes;
+  int rec_off = -1;   // >= 0: a field of the env records (mc::EnvRec), not an array of its own
+  int rec_width = 0;  // its bytes per env (4 or 8)
 };
+
+// copy a field between the env and the caller's contiguous buffer
+int copy_field(Env* E, const FieldDesc& d, void* buf, bool to_env, hipStream_t st) {
+  if (d.rec_off >= 0) {
+    HIP_TRY(mc::launch_rec_field(E->s, d.rec_off, d.rec_width, buf, to_env, st));
+    return MC_OK;
+  }
+  HIP_TRY(hipMemcpyAsync(to_env ? d.ptr : buf, to_env ? buf : d.ptr, (size_t)d.bytes, hipMemcpyDeviceToDevice, st));
+  return MC_OK;
+}
 
 FieldDesc field(Env* E, int f) {
   const mc::State& s = E->s;
   const int64_t B = s.B, N = s.N, mw = s.MT, G = s.G;
+#define REC_FIELD(name) \
+  FieldDesc { s.rec, B * (int64_t)sizeof(s.rec->name), (int)offsetof(mc::EnvRec, name), (int)sizeof(s.rec->name) }
   switch (f) {
     case MC_FIELD_POS: return {s.pos, B * N * 2 * 4};
-    case MC_FIELD_MOVED: return {s.moved, B * 8};
+    case MC_FIELD_MOVED: return REC_FIELD(moved);
     case MC_FIELD_FREE: return {s.freem, B * N * mw * 8};
     case MC_FIELD_OBST: return {s.obstm, B * N * mw * 8};
     case MC_FIELD_VISITED: return {s.vis, B * mw * 8};
-    case MC_FIELD_FREE_COUNT: return {s.free_cnt, B * 4};
-    case MC_FIELD_VISITED_COUNT: return {s.vis_cnt, B * 4};
-    case MC_FIELD_CURRSTEP: return {s.currstep, B * 4};
-    case MC_FIELD_DONE_THRESH: return {s.done_thresh, B * 8};
-    case MC_FIELD_ENV_GRID: return {s.env_grid, B * 4};
-    case MC_FIELD_EPISODE: return {s.episode, B * 4};
+    case MC_FIELD_FREE_COUNT: return REC_FIELD(free_cnt);
+    case MC_FIELD_VISITED_COUNT: return REC_FIELD(vis_cnt);
+    case MC_FIELD_CURRSTEP: return REC_FIELD(currstep);
+    case MC_FIELD_DONE_THRESH: return REC_FIELD(done_thresh);
+    case MC_FIELD_ENV_GRID: return REC_FIELD(env_grid);
+    case MC_FIELD_EPISODE: return REC_FIELD(episode);
     case MC_FIELD_NUMFREE: return {(void*)s.numfree, G * 4};
     case MC_FIELD_GRID_NEG: return {(void*)s.grid_neg, G * mw * 8};
     case MC_FIELD_GRID_POS: return {(void*)s.grid_pos, G * mw * 8};
@@ -128,6 +143,7 @@ FieldDesc field(Env* E, int f) {
     case MC_FIELD_DIST_TOTALS: return {s.dist_tot, s.dist_tot ? 32 : -1};
     default: return {nullptr, -1};
   }
+#undef REC_FIELD
 }
 
 int dev_alloc(Env* E, void** p, size_t bytes) {
@@ -324,19 +340,13 @@ int mc_create(const mc_config* cfg, int hip_device, void** out_env) {
   ALLOC(gneg, uint64_t, G * mw);
   ALLOC(gpos, uint64_t, G * mw);
   ALLOC(nfree, int32_t, G);
-  ALLOC(s.env_grid, int32_t, B);
+  ALLOC(s.rec, mc::EnvRec, B);
   ALLOC(s.pos, int32_t, B * N * 2);
-  ALLOC(s.moved, uint64_t, B);
   // one extra tile past each mask array stays zero: the env kernel's staged
   // tiles outside the map read it (no select on the loaded value)
   ALLOC(s.freem, uint64_t, B * N * mw + 1);
   ALLOC(s.obstm, uint64_t, B * N * mw + 1);
   ALLOC(s.vis, uint64_t, B * mw + 1);
-  ALLOC(s.free_cnt, uint32_t, B);
-  ALLOC(s.vis_cnt, uint32_t, B);
-  ALLOC(s.currstep, int32_t, B);
-  ALLOC(s.done_thresh, double, B);
-  ALLOC(s.episode, uint32_t, B);
   ALLOC(s.err, uint32_t, 4);
   ALLOC(s.ep_pc, double, B);
   ALLOC(s.ep_len, int32_t, B);
@@ -350,11 +360,12 @@ int mc_create(const mc_config* cfg, int hip_device, void** out_env) {
     return fail(rc, "%s", msg.c_str());
   }
   {
-    std::vector<int32_t> eg(B);
-    for (size_t i = 0; i < B; ++i) eg[i] = (int32_t)(i % G);
-    std::vector<double> dt(B, c.done_thresh);
-    if (hipMemcpy(s.env_grid, eg.data(), B * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(s.done_thresh, dt.data(), B * 8, hipMemcpyHostToDevice) != hipSuccess) {
+    std::vector<mc::EnvRec> recs(B);  // (value-initialised: zero)
+    for (size_t i = 0; i < B; ++i) {
+      recs[i].env_grid = (int32_t)(i % G);
+      recs[i].done_thresh = c.done_thresh;
+    }
+    if (hipMemcpy(s.rec, recs.data(), B * sizeof(mc::EnvRec), hipMemcpyHostToDevice) != hipSuccess) {
       mc_destroy(E);
       return fail(MC_EHIP, "mc_create: initial upload failed");
     }
@@ -907,8 +918,8 @@ int mc_set_env_grids(void* env, const int32_t* dev_env_grid, void* stream) {
   Env* E = as_env(env);
   if (!E || !dev_env_grid) return fail(MC_EINVAL, "mc_set_env_grids: null argument");
   HIP_TRY(hipSetDevice(E->device));
-  HIP_TRY(hipMemcpyAsync(E->s.env_grid, dev_env_grid, (size_t)E->s.B * 4, hipMemcpyDeviceToDevice,
-                         (hipStream_t)stream));
+  HIP_TRY(mc::launch_rec_field(E->s, (int)offsetof(mc::EnvRec, env_grid), 4, const_cast<int32_t*>(dev_env_grid),
+                               /*to_rec=*/true, (hipStream_t)stream));
   return MC_OK;
 }
 
@@ -1036,8 +1047,7 @@ int mc_get_state(void* env, int32_t f, void* dev_dst, int64_t bytes, void* strea
   if (!d.ptr) return fail(MC_EINVAL, "unknown state field %d", f);
   if (bytes != d.bytes) return fail(MC_EINVAL, "field %d is %lld bytes, got %lld", f, (long long)d.bytes, (long long)bytes);
   HIP_TRY(hipSetDevice(E->device));
-  HIP_TRY(hipMemcpyAsync(dev_dst, d.ptr, (size_t)bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return MC_OK;
+  return copy_field(E, d, dev_dst, /*to_env=*/false, (hipStream_t)stream);
 }
 
 int mc_set_state(void* env, int32_t f, const void* dev_src, int64_t bytes, void* stream) {
@@ -1050,7 +1060,7 @@ int mc_set_state(void* env, int32_t f, const void* dev_src, int64_t bytes, void*
     return fail(MC_EINVAL, "field %d is derived state (read-only)", f);
   if (bytes != d.bytes) return fail(MC_EINVAL, "field %d is %lld bytes, got %lld", f, (long long)d.bytes, (long long)bytes);
   HIP_TRY(hipSetDevice(E->device));
-  HIP_TRY(hipMemcpyAsync(d.ptr, dev_src, (size_t)bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  if (int rc = copy_field(E, d, const_cast<void*>(dev_src), /*to_env=*/true, (hipStream_t)stream); rc != MC_OK) return rc;
   if (f == MC_FIELD_GRID_NEG || f == MC_FIELD_GRID_POS || f == MC_FIELD_NUMFREE) E->grids_set = true;
   E->dist_pre_stale = true;  // uploaded maps / positions: recompute the PRE terms
   if (E->s.dist_mw)  // and max(d) of every map

@@ -1607,14 +1607,14 @@ __device__ __forceinline__ void reset_env(const State& s, const Ctx<NT, EPW, WT>
   const int N = s.N;
   const int e = C.e;
   if (C.sub == 0) {
-    const uint32_t ep = s.episode[e] + 1u;
-    s.episode[e] = ep;
+    const uint32_t ep = s.rec[e].episode + 1u;
+    s.rec[e].episode = ep;
     L.sc->ep = ep;
     if (s.grid_mode == 1) {
       const uint4 r = philox(s.seed, make_uint4(0xFFFFFFFFu, s.env0 + (uint32_t)e, ep, 0x67726964u));
       const int g = (int)bounded(r.x, (uint32_t)s.G);
       L.sc->grid = g;
-      s.env_grid[e] = g;
+      s.rec[e].env_grid = g;
     }
     L.sc->moved = 0;
     L.sc->cnt_free = 0;
@@ -1679,9 +1679,9 @@ __device__ __forceinline__ void reset_env(const State& s, const Ctx<NT, EPW, WT>
   store_tiles<NT, EPW, WT, KI, O32>(s, C, I);
   __syncthreads();
   if (C.sub == 0) {
-    s.free_cnt[e] = L.sc->cnt_free;
-    s.vis_cnt[e] = L.sc->cnt_vis;
-    s.currstep[e] = 0;
+    s.rec[e].free_cnt = L.sc->cnt_free;
+    s.rec[e].vis_cnt = L.sc->cnt_vis;
+    s.rec[e].currstep = 0;
   }
 }
 
@@ -1996,11 +1996,13 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
   const int2 p0 = el<O32>(reinterpret_cast<const int2*>(s.pos), eN + ag);
   const int act_raw = el<O32>(ab, is_step ? eN + ag : 0), act0_raw = el<O32>(ab, is_step ? eN : 0);
   const int req_raw = mb[0];
-  const int g0 = el<O32>(s.env_grid, e);
-  const uint64_t moved0 = el<O32>(s.moved, e);
-  const uint32_t free_old = el<O32>(s.free_cnt, e), vis_old = el<O32>(s.vis_cnt, e);
-  const int currstep0 = el<O32>(s.currstep, e);
-  const double dthresh0 = el<O32>(s.done_thresh, e);
+  const RecLo rl0 = rec_lo(el<O32>(s.rec, e));  // the env's record: two 16-byte loads
+  const RecHi rh0 = rec_hi(el<O32>(s.rec, e));
+  const int g0 = rh0.env_grid;
+  const uint64_t moved0 = rh0.moved;
+  const uint32_t free_old = rl0.free_cnt, vis_old = rl0.vis_cnt;
+  const int currstep0 = rh0.currstep;
+  const double dthresh0 = rl0.done_thresh;
   const bool lidar = s.sensor == 0;
   const int nbl = lidar ? s.nbeams : 1;  // a square env reads a dummy record
   const int4 bm0 = reinterpret_cast<const int4*>(lidar ? (const void*)s.beams : (const void*)s.pos)
@@ -2160,10 +2162,11 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
     int currstep_r = currstep0;
     double dthresh_r = dthresh0;
     if constexpr (EPW == 1) {
-      free_old_r = el<O32>(s.free_cnt, e);
-      vis_old_r = el<O32>(s.vis_cnt, e);
-      currstep_r = el<O32>(s.currstep, e);
-      dthresh_r = el<O32>(s.done_thresh, e);
+      const RecLo rl = rec_lo(el<O32>(s.rec, e));
+      free_old_r = rl.free_cnt;
+      vis_old_r = rl.vis_cnt;
+      currstep_r = el<O32>(s.rec, e).currstep;
+      dthresh_r = rl.done_thresh;
     }
     float dpre0 = 0.0f, dprek = 0.0f;
     if (kPrePrefetch && s.dist && C.sub < N) {
@@ -2230,10 +2233,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
           el<O32>(s.ep_pc, e) = exact1 ? (double)fc / (double)numfree : pc;
           el<O32>(s.ep_len, e) = cs;
         }
-        el<O32>(s.free_cnt, e) = fc;
-        el<O32>(s.vis_cnt, e) = vc;
-        el<O32>(s.currstep, e) = cs;
-        el<O32>(s.done_thresh, e) = dt;
+        rec_store_counts(el<O32>(s.rec, e), dt, fc, vc, cs);
         c->do_reset = do_reset ? 1 : 0;
       }
     }
@@ -2319,7 +2319,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
   if (p_active || p_reset_req || p_sent_reset) {
     if (C.sub < N)
       el<O32>(reinterpret_cast<int2*>(s.pos), (uint32_t)e * (uint32_t)N + C.sub) = make_int2(L.x[C.sub], L.y[C.sub]);
-    if (C.sub == 0) el<O32>(s.moved, e) = L.sc->moved;
+    if (C.sub == 0) el<O32>(s.rec, e).moved = L.sc->moved;
     // dist_reward: a reset map, or one whose witness got closer than M,
     // has an unknown M now (recomputed by the full transform, mc_dist.hip)
     if (s.dist && C.sub < N &&

@@ -57,7 +57,7 @@ __global__ __launch_bounds__(64) void share_kernel(State s, const uint8_t* __res
     if (fn != fi) f[i * mw] = fn;
     if (on != oi) o[i * mw] = on;
   }
-  if (cnt) atomicAdd(&s.free_cnt[e], cnt);
+  if (cnt) atomicAdd(&s.rec[e].free_cnt, cnt);
 }
 
 // --------------------------------------------------------------------------
@@ -143,6 +143,26 @@ __global__ void random_actions_kernel(State s, uint64_t seed, uint32_t step, uin
 hipError_t launch_random_actions(const State& s, uint64_t seed, int step, uint8_t* out, hipStream_t stream) {
   hipLaunchKernelGGL(random_actions_kernel, dim3((s.B + 255) / 256), dim3(256), 0, stream, s, seed,
                      (uint32_t)step, out);
+  return hipGetLastError();
+}
+
+// One field of the env records (EnvRec bytes [off, off + width), width 4 or
+// 8) from / to a contiguous [B] buffer: mc_get_state / mc_set_state
+template <typename T>
+__global__ void rec_field_kernel(EnvRec* rec, int off, T* buf, int B, int to_rec) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= B) return;
+  T* f = reinterpret_cast<T*>(reinterpret_cast<char*>(rec + e) + off);
+  if (to_rec) *f = buf[e];
+  else buf[e] = *f;
+}
+
+hipError_t launch_rec_field(const State& s, int off, int width, void* buf, bool to_rec, hipStream_t stream) {
+  const dim3 grid((s.B + 255) / 256), block(256);
+  if (width == 8)
+    hipLaunchKernelGGL(rec_field_kernel<uint64_t>, grid, block, 0, stream, s.rec, off, (uint64_t*)buf, s.B, to_rec ? 1 : 0);
+  else
+    hipLaunchKernelGGL(rec_field_kernel<uint32_t>, grid, block, 0, stream, s.rec, off, (uint32_t*)buf, s.B, to_rec ? 1 : 0);
   return hipGetLastError();
 }
 

@@ -2,6 +2,7 @@
 // C ABI (mc_capi.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace mc {
@@ -37,6 +38,24 @@ struct Beam {
 static_assert(sizeof(Beam) == 16, "Beam is 16 bytes");
 
 
+// The step's per-env scalars, one 64-byte line per env (State::rec): the env
+// kernel's first round trip reads them with two 16-byte loads (rec_lo,
+// rec_hi) and its reward writes them back with one 16-byte and one 4-byte
+// store, instead of one cold line per field and env.
+struct alignas(64) EnvRec {
+  double done_thresh;  // bytes 0-15: rec_lo
+  uint32_t free_cnt;   // set bits over all agents' free maps
+  uint32_t vis_cnt;    // covered union cells
+  int32_t currstep;    // bytes 16-31: rec_hi
+  int32_t env_grid;    // the env's grid in the pool
+  uint64_t moved;      // robots present in the reference's _robot_pad
+  uint32_t episode;
+  uint32_t unused_[7];
+};
+static_assert(sizeof(EnvRec) == 64 && alignof(EnvRec) == 64, "EnvRec is one 64-byte line");
+static_assert(offsetof(EnvRec, free_cnt) == 8 && offsetof(EnvRec, currstep) == 16 && offsetof(EnvRec, moved) == 24,
+              "rec_lo / rec_hi read EnvRec's first two 16-byte quarters");
+
 // Bit maps are stored as 8x8-cell tiles: one u64 per tile, bit 8*r + c =
 // cell (8*ti + r, 8*tj + c).  Tiles are grouped 4 x 4 into 128-byte blocks
 // (one cache line; row-major blocks, row-major tiles inside a block:
@@ -52,6 +71,7 @@ static_assert(sizeof(Beam) == 16, "Beam is 16 bytes");
 // (each mask array has one more tile at its end that is always zero)
 // with MT = TRS * TCS * 16 tiles per map in tile_index order.
 //   pos                i32 [B][N][2]       (_xinds, _yinds)
+//   rec                EnvRec [B]          moved, done_thresh, counters, grid, episode
 struct State {
   int B, N, Wp, Lp, G;
   int TR, TC;              // tile rows / columns of a map: ceil(Wp/8), ceil(Lp/8)
@@ -96,17 +116,11 @@ struct State {
   // fan_words words in all (a multiple of 4), copied into LDS each launch.
   int fan_nsec, fan_nspec, fan_kt, fan_words;
   const uint32_t* fan_data;
-  int32_t* env_grid;
+  EnvRec* rec;             // [B] the per-env scalars
   int32_t* pos;
-  uint64_t* moved;
   uint64_t* freem;
   uint64_t* obstm;
   uint64_t* vis;
-  uint32_t* free_cnt;
-  uint32_t* vis_cnt;
-  int32_t* currstep;
-  double* done_thresh;
-  uint32_t* episode;
   uint32_t* err;
   uint64_t* stamps;        // diagnostic builds (-DMC_STAMPS) only: [B][16] s_memtime
   const float* dist_pre;   // dist_reward: [B][N][8] max(d), d of the 5 end cells (mc_dist.hip)
@@ -170,6 +184,31 @@ struct State {
   double* ep_pc;
   int32_t* ep_len;
 };
+
+// EnvRec's first / second 16 bytes as one load each, and their fields
+struct RecLo {
+  double done_thresh;
+  uint32_t free_cnt, vis_cnt;
+};
+struct RecHi {
+  int32_t currstep, env_grid;
+  uint64_t moved;
+};
+__device__ __forceinline__ RecLo rec_lo(const EnvRec& r) {
+  const int4 v = *reinterpret_cast<const int4*>(&r);
+  return RecLo{__hiloint2double(v.y, v.x), (uint32_t)v.z, (uint32_t)v.w};
+}
+__device__ __forceinline__ RecHi rec_hi(const EnvRec& r) {
+  const int4 v = *(reinterpret_cast<const int4*>(&r) + 1);
+  return RecHi{v.x, v.y, (uint64_t)(uint32_t)v.z | ((uint64_t)(uint32_t)v.w << 32)};
+}
+// the reward's write-back: done_thresh and the counters (one store), currstep
+__device__ __forceinline__ void rec_store_counts(EnvRec& r, double done_thresh, uint32_t free_cnt, uint32_t vis_cnt,
+                                                 int32_t currstep) {
+  *reinterpret_cast<int4*>(&r) =
+      make_int4(__double2loint(done_thresh), __double2hiint(done_thresh), (int)free_cnt, (int)vis_cnt);
+  r.currstep = currstep;
+}
 
 constexpr int kMaxItemsPerLane = 2;  // staged (agent, tile) items per lane
 #ifndef MC_DIST_K  // build-time tuning constants (tools/build_variants.py)

@@ -1,9 +1,9 @@
 # A/B of variant libraries (tools/build_variants.py) at C2, alternating runs:
-#   VARIANTS="base nt" [EXTRA="HIP_FORCE_DEV_KERNARG=1"] bash tools/gpu_ab_pair.sh
+#   VARIANTS="base nt" [REPS=3] [EXTRA="HIP_FORCE_DEV_KERNARG=1"] bash tools/gpu_ab_pair.sh
 set -u
 R="$GRAFT_REPO_ROOT"; OUT="$R/gpurun_out/abpair"; mkdir -p "$OUT"
 cd "$R"
-for rep in 1 2 3; do
+for rep in $(seq 1 ${REPS:-3}); do
   for v in ${VARIANTS}; do
     for k in "200 20" "20 5"; do
       set -- $k
