@@ -172,12 +172,58 @@ __device__ __forceinline__ int row_word(const State& s, int a, int lx) {
   return sizeof(WT) == 4 ? lx * (s.N | 1) + a : a * (8 * s.TW + 1) + lx;
 }
 
-// one env slot of the workgroup
-template <int NT, int EPW, typename WT>
+// whether a compile-time obs shape takes write_obs_fast (see there)
+template <int EGO, int NS, int LC = 3>
+struct ObsFast {
+  static constexpr int E = 2 * EGO + 1, EE = E * E, NB = LC * NS;
+  static constexpr bool ok = EGO > 0 && NS > 0 && EE <= 28 && (NB * EE) % 4 == 0 && (LC == 3 || LC == 4);
+};
+
+// One env slot of the workgroup, and everything fixed at compile time for one
+// env_kernel<NT, EPW, WT, SH> instantiation: the device functions take a
+// `const CT& C` and read their constants from CT, not from template arguments.
+template <int NT_, int EPW_, typename WT_, class SH_>
 struct Ctx {
+  using WT = WT_;  // a window row's word (u32: TW <= 4, else u64)
+  using SH = SH_;  // the compiled Shape (mc_internal.h; Dynamic: nothing baked in)
+  static constexpr int NT = NT_, EPW = EPW_;      // workgroup lanes, envs per workgroup
   static constexpr int LPE = NT / EPW;            // lanes per env
   static constexpr int KI = kMaxItemsPerLane;     // staged tiles per lane
-  static constexpr int RPL = EPW == 1 ? 2 : 3;  // beams per lane per pass (C4 A/B: 3, 4 or 6 are slower)
+  static constexpr int RPL0 = EPW == 1 ? 2 : 3;  // beams per lane per pass (C4 A/B: 3, 4 or 6 are slower)
+  static constexpr int KM = SH::KM, KN = SH::KN;  // the shape's beam_kmax (fan trip count) and beam_kmin; 0: runtime
+  // march steps per batch: the whole march when the shape fixes a short
+  // beam_kmax, a quarter of a long one (register pressure)
+  static constexpr int SUK0 = (SH::KM > 0 && SH::KM <= 12) ? SH::KM : (SH::KM > 12 ? (SH::KM + 3) / 4 : 8);
+  // compile-time agent count, if small (merge, the register front); the
+  // moves, dist_window_am2 and the obs read SH::N under bounds of their own
+  static constexpr int NSM = (SH::N > 0 && SH::N <= 8) ? SH::N : 0;
+  // rays per lane per march pass: 3 where that saves a pass over the
+  // default (C5: 336 rays over 128 lanes, one pass of 3 instead of two of 2)
+  static constexpr int RPLK = SH::N > 0 && SH::NB > 0 && SH::NB < 64 && EPW == 1 &&
+                                      (SH::N * SH::NB + 3 * NT - 1) / (3 * NT) < (SH::N * SH::NB + RPL0 * NT - 1) / (RPL0 * NT)
+                                  ? 3
+                                  : 0;
+  static constexpr int RPL = RPLK > 0 ? RPLK : RPL0;
+  // (3 rays per lane: half the march's batch, the row words of a batch stay
+  // within the register budget)
+  static constexpr int SUK = RPLK == 3 ? (SUK0 + 1) / 2 : SUK0;
+  // compiled shapes with up to 8 agents: map byte offsets fit 32 bits
+  // (launch_env checks; the C5 shape's maps pass 4 GB)
+  static constexpr bool O32 = SH::N > 0 && SH::N <= 8;
+  // register front (front_regs / moves_front): compiled agent count <= 8, one wave per workgroup
+  static constexpr bool FRONT = NSM > 0 && NT == 64;
+  // moves from registers in the first wave of a multi-wave env during round
+  // trip 2 (compiled agent count <= 8, lidar: C4)
+  static constexpr bool EARLY = NSM > 0 && NT > 64 && EPW == 1 && SH::NB > 0;
+  // dist_reward: lane i < N loads its agent's PRE terms right after the moves
+  // (compiled shapes; the generic kernels keep the loads in the reward:
+  // two more live registers there cost the u64 ones a wave per SIMD)
+  static constexpr bool kPrePrefetch = SH::N > 0;
+  // the obs: write_obs_fast for a compile-time obs shape whose crops fit the
+  // first wave, else write_obs with the robots in registers up to 16 agents
+  static constexpr bool OBS_FAST = ObsFast<SH::EGO, SH::N, SH::LC>::ok && (NT == 64 || EPW == 1) &&
+                                   ObsFast<SH::EGO, SH::N, SH::LC>::NB <= 64;
+  static constexpr int NS_OBS = (SH::N > 0 && SH::N <= 16) ? SH::N : 0;
   int sub;    // lane within the env
   int lane0;  // first lane of this env's slot within the wave
   int e;      // env index
@@ -185,18 +231,18 @@ struct Ctx {
 };
 
 // broadcast lane (lane0 + i)'s value of v to the slot
-template <int NT, int EPW, typename WT>
-__device__ __forceinline__ int bcast(const Ctx<NT, EPW, WT>& C, int v, int i) {
-  if constexpr (EPW == 1) return rdlane(v, i);
+template <class CT>
+__device__ __forceinline__ int bcast(const CT& C, int v, int i) {
+  if constexpr (CT::EPW == 1) return rdlane(v, i);
   else return __shfl(v, C.lane0 + i);
 }
 
 // ballot restricted to this env's slot (bit j = lane lane0 + j)
-template <int NT, int EPW, typename WT>
-__device__ __forceinline__ uint64_t slot_ballot(const Ctx<NT, EPW, WT>& C, bool p) {
+template <class CT>
+__device__ __forceinline__ uint64_t slot_ballot(const CT& C, bool p) {
   const uint64_t m = __ballot(p);
-  if constexpr (EPW == 1) return m;
-  else return (m >> C.lane0) & low_mask(Ctx<NT, EPW, WT>::LPE);
+  if constexpr (CT::EPW == 1) return m;
+  else return (m >> C.lane0) & low_mask(CT::LPE);
 }
 
 // staged (agent, tile) items of this lane; old HBM tiles stay in registers
@@ -292,12 +338,12 @@ __device__ __forceinline__ int pick(const int (&R)[NS], int a) {
 
 // the value v of lane lane0 + i of this lane's slot, read with wave-uniform
 // lane indices (v_readlane) and selected by slot
-template <int NT, int EPW, typename WT>
-__device__ __forceinline__ int slot_lane(const Ctx<NT, EPW, WT>& C, int v, int i) {
-  static_assert(NT == 64 || EPW == 1, "one wave per workgroup, or the first wave of one env");
-  if constexpr (EPW == 1) return rdlane(v, i);
+template <class CT>
+__device__ __forceinline__ int slot_lane(const CT& C, int v, int i) {
+  static_assert(CT::NT == 64 || CT::EPW == 1, "one wave per workgroup, or the first wave of one env");
+  if constexpr (CT::EPW == 1) return rdlane(v, i);
   else {
-    static_assert(EPW == 2, "two slots per wave");
+    static_assert(CT::EPW == 2, "two slots per wave");
     const int lo = rdlane(v, i), hi = rdlane(v, 32 + i);
     return C.lane0 ? hi : lo;
   }
@@ -321,9 +367,8 @@ __device__ __forceinline__ int quad_bcast(int v, int i) {  // i: a constant once
   }
 }
 
-template <int NT, int EPW, typename WT, int NS>
-__device__ __forceinline__ void front_regs(const State& s, const Ctx<NT, EPW, WT>& C, int x, int y, int act,
-                                           Front<NS>& F) {
+template <class CT, int NS>
+__device__ __forceinline__ void front_regs(const State& s, const CT& C, int x, int y, int act, Front<NS>& F) {
   const int xy = (int)((uint32_t)x | ((uint32_t)y << 16));
 #pragma unroll
   for (int i = 0; i < NS; ++i) {
@@ -341,12 +386,14 @@ __device__ __forceinline__ void front_regs(const State& s, const Ctx<NT, EPW, WT
 
 // round trip 2, issue: addresses, then every load of the lane back to back
 // with no exec-mask branches (tiles outside the map read tile 0 and are
-// replaced in stage_scatter).  NS > 0: block origins from F (registers),
-// else from LDS (L.bx / L.by, written after round trip 1).
-template <int NT, int EPW, typename WT, int KI, bool O32 = false, int NS = 0>
-__device__ __forceinline__ void stage_load(const State& s, const Ctx<NT, EPW, WT>& C, int g,
-                                           bool load_masks, Items<KI>& I, const Front<NS>* F = nullptr) {
-  constexpr int LPE = Ctx<NT, EPW, WT>::LPE;
+// replaced in stage_scatter).  Block origins from F (registers) where the
+// caller has a register front (NS > 0, deduced from F), else from LDS
+// (L.bx / L.by, written after round trip 1).
+template <class CT, int NS = 0, typename WT = typename CT::WT>
+__device__ __forceinline__ void stage_load(const State& s, const CT& C, int g, bool load_masks,
+                                           Items<CT::KI>& I, const Front<NS>* F = nullptr) {
+  constexpr int LPE = CT::LPE, KI = CT::KI;
+  constexpr bool O32 = CT::O32;
   const Lds<WT>& L = C.L;
   const int TW = s.TW, TW2 = TW * TW;
   const int items = s.N * TW2;
@@ -425,9 +472,10 @@ __device__ __forceinline__ uint64_t transpose8(uint64_t x) {
 
 // round trip 2, landing: the grid tiles into the row planes (and the tile
 // planes for the square sensor; the column planes for the fan march)
-template <int NT, int EPW, typename WT, int KI>
-__device__ __forceinline__ void stage_scatter(const State& s, const Ctx<NT, EPW, WT>& C, Items<KI>& I) {
-  constexpr int LPE = Ctx<NT, EPW, WT>::LPE;
+template <class CT, typename WT = typename CT::WT>
+__device__ __forceinline__ void stage_scatter(const State& s, const CT& C, Items<CT::KI>& I) {
+  constexpr int LPE = CT::LPE, KI = CT::KI;
+  [[maybe_unused]] constexpr int EPW = CT::EPW;  // STAMP
   const Lds<WT>& L = C.L;
   const int items = s.N * s.TW * s.TW;
   const bool square = s.sensor == 1;
@@ -478,45 +526,33 @@ __device__ __forceinline__ void stage_scatter(const State& s, const Ctx<NT, EPW,
   }
 }
 
-template <int NT, int EPW, typename WT, int KI, bool O32 = false>
-__device__ __forceinline__ void stage(const State& s, const Ctx<NT, EPW, WT>& C, int g,
-                                      bool load_masks, Items<KI>& I) {
-  stage_load<NT, EPW, WT, KI, O32>(s, C, g, load_masks, I);
-  stage_scatter<NT, EPW, WT, KI>(s, C, I);
+template <class CT>
+__device__ __forceinline__ void stage(const State& s, const CT& C, int g, bool load_masks, Items<CT::KI>& I) {
+  stage_load(s, C, g, load_masks, I);
+  stage_scatter(s, C, I);
 }
 
-// old mask tiles of item k (zero outside the map, where nothing is stored:
-// such items loaded the arrays' zero tile; without mask loads they are 0)
-template <int KI>
-__device__ __forceinline__ void old_tiles(const Items<KI>& I, int k, uint64_t& f, uint64_t& o,
-                                          uint64_t& u) {
-  f = I.f[k];
-  o = I.o[k];
-  u = I.u[k];
-}
-
-// the old free / obstacle tiles into LDS (obs of an env that does not step)
-template <int NT, int EPW, typename WT, int KI>
-__device__ __forceinline__ void stage_fold(const State& s, const Ctx<NT, EPW, WT>& C,
-                                           const Items<KI>& I) {
-  constexpr int LPE = Ctx<NT, EPW, WT>::LPE;
+// the old free / obstacle tiles into LDS (obs of an env that does not step).
+// I.f / I.o / I.u are zero outside the map, where nothing is stored: such items
+// loaded the arrays' zero tile; without mask loads they are 0.
+template <class CT>
+__device__ __forceinline__ void stage_fold(const State& s, const CT& C, const Items<CT::KI>& I) {
+  constexpr int LPE = CT::LPE, KI = CT::KI;
   const int items = s.N * s.TW * s.TW;
 #pragma unroll
   for (int k = 0; k < KI; ++k) {
     const int idx = C.sub + k * LPE;
     if (idx < items) {
-      uint64_t f, o, u;
-      old_tiles<KI>(I, k, f, o, u);
-      C.L.fold[idx] = f;
-      C.L.oold[idx] = o;
+      C.L.fold[idx] = I.f[k];
+      C.L.oold[idx] = I.o[k];
     }
   }
 }
 
 // lidar mark rows start empty (LDS stores: issued while loads are in flight)
-template <int NT, int EPW, typename WT>
-__device__ __forceinline__ void zero_marks(const State& s, const Ctx<NT, EPW, WT>& C) {
-  constexpr int LPE = Ctx<NT, EPW, WT>::LPE;
+template <class CT, typename WT = typename CT::WT>
+__device__ __forceinline__ void zero_marks(const State& s, const CT& C) {
+  constexpr int LPE = CT::LPE;
   if (s.sensor != 0) return;
   const bool fan = fan_on(s);
   for (int r = C.sub; r < row_plane_words(s.N, s.TW, (int)sizeof(WT)); r += LPE) {
@@ -565,8 +601,8 @@ __device__ __forceinline__ uint64_t gather_tile(const WT* rows, int w0, int rs, 
 // higher-index robot that has not moved yet (:186,190-199,310).  The grid
 // test reads the staged window (1 outside the map = isInBounds).
 // --------------------------------------------------------------------------
-template <int NT, int EPW, typename WT>
-__device__ __forceinline__ void moves(const State& s, const Ctx<NT, EPW, WT>& C, double pen_unit) {
+template <class CT, typename WT = typename CT::WT>
+__device__ __forceinline__ void moves(const State& s, const CT& C, double pen_unit) {
   const Lds<WT>& L = C.L;
   const int N = s.N;
   const bool live = C.sub < N;
@@ -599,7 +635,7 @@ __device__ __forceinline__ void moves(const State& s, const Ctx<NT, EPW, WT>& C,
 #define MC_ABL 0  // merge, 3 no overlap dedup in merge, 4 no obs, 5 no sensing march
 #endif
 
-// Same moves for a compile-time agent count NS > 8 with one env per
+// Same moves for a compile-time agent count NS = SH::N > 8 with one env per
 // workgroup (C5: 16 robots), by a fixed point instead of N serial broadcast
 // rounds.  Robot i moves iff its action is a move (0..3), its target is not
 // blocked (grid < 0, out of bounds) and no robot sits on the target at its
@@ -612,9 +648,10 @@ __device__ __forceinline__ void moves(const State& s, const Ctx<NT, EPW, WT>& C,
 // between robots ends after one round and its check.  Lane i = robot i of
 // the first wave; each round is NS compares per lane against the robots'
 // cells read as scalars (v_readlane), one ballot.
-template <int NT, int EPW, typename WT, int NS>
-__device__ __forceinline__ void moves_par(const State& s, const Ctx<NT, EPW, WT>& C, double pen_unit) {
-  static_assert(EPW == 1 && NS > 0 && NS <= 64, "one env per workgroup, compile-time robots <= 64");
+template <class CT, typename WT = typename CT::WT>
+__device__ __forceinline__ void moves_par(const State& s, const CT& C, double pen_unit) {
+  constexpr int NS = CT::SH::N;
+  static_assert(CT::EPW == 1 && NS > 0 && NS <= 64, "one env per workgroup, compile-time robots <= 64");
   const Lds<WT>& L = C.L;
   const int i = C.sub;  // lane of the first wave
   const bool live = i < NS;
@@ -666,11 +703,12 @@ __device__ __forceinline__ void moves_par(const State& s, const Ctx<NT, EPW, WT>
   }
 }
 
-// Same moves for a compile-time agent count NS <= 8: every lane of the slot
-// replays the robot-order loop on all robots' data in registers (no
+// Same moves for a compile-time agent count NS = SH::N <= 8: every lane of
+// the slot replays the robot-order loop on all robots' data in registers (no
 // cross-lane traffic); lane 0 publishes the result.
-template <int NT, int EPW, typename WT, int NS>
-__device__ __forceinline__ void moves_regs(const State& s, const Ctx<NT, EPW, WT>& C, double pen_unit) {
+template <class CT, typename WT = typename CT::WT>
+__device__ __forceinline__ void moves_regs(const State& s, const CT& C, double pen_unit) {
+  constexpr int NS = CT::SH::N;
   const Lds<WT>& L = C.L;
   int X[NS], Y[NS], DX[NS], DY[NS];
   bool acts[NS], blk[NS];
@@ -716,11 +754,10 @@ __device__ __forceinline__ void moves_regs(const State& s, const Ctx<NT, EPW, WT
 // bounds) was loaded by lane lane0 + i next to round trip 2 and is shared by
 // a ballot; every lane of the slot replays the robot-order loop; lane 0
 // publishes the result.  Same semantics as moves_regs.
-template <int NT, int EPW, typename WT, int NS>
-__device__ __forceinline__ void moves_front(const State& s, const Ctx<NT, EPW, WT>& C, const Front<NS>& F,
-                                            bool tgt_blk, uint32_t txy, int act_own, uint64_t moved,
-                                            double pen_unit) {
-  const Lds<WT>& L = C.L;
+template <class CT, int NS>
+__device__ __forceinline__ void moves_front(const State& s, const CT& C, const Front<NS>& F, bool tgt_blk,
+                                            uint32_t txy, int act_own, uint64_t moved, double pen_unit) {
+  const Lds<typename CT::WT>& L = C.L;
   // QUAD: every lane holds its quad's robot (sub % NS): its packed target
   // and flags (bit 0 blocked, bit 1 acts) go to the loop by quad_perm
   const int fl = (tgt_blk ? 1 : 0) | (act_own <= 3 ? 2 : 0);
@@ -838,12 +875,13 @@ __device__ __forceinline__ const WT* ray_word(const Lds<WT>& L, const WT* plane,
 // cells: fewer same-address LDS atomics).  `premarked`: the cell is one of the
 // step-1 cells sense() marked once per agent (State::beam_k1).  Returns
 // whether the ray marked.
-template <typename WT, int KN>
-__device__ __forceinline__ bool ray_mark(const Lds<WT>& L, Ray& R, int k, WT nrow, WT frow,
-                                         uint32_t sink_m, bool dup, bool frow_valid, bool premarked) {
+template <class CT, typename WT = typename CT::WT>
+__device__ __forceinline__ bool ray_mark(const CT& C, Ray& R, int k, WT nrow, WT frow, uint32_t sink_m, bool dup,
+                                         bool frow_valid, bool premarked) {
+  const Lds<WT>& L = C.L;
   // KN: a compile-time lower bound of every beam's K (steps k <= KN need no
   // range test)
-  const bool on = R.live && (k <= KN || k <= R.K);
+  const bool on = R.live && (k <= CT::KN || k <= R.K);
   const WT bit = (WT)1 << (R.P & (8 * sizeof(WT) - 1));
   const bool hit = (nrow & bit) != 0;  // oc[int(cx), int(cy)] < 0: the beam ends here
   dup |= (frow & bit) != 0;  // a cell the agent has seen: its mark is known (frow: 0 unless dense)
@@ -903,10 +941,11 @@ __device__ __forceinline__ T* lds_ptr(uint32_t a) {
 // entries T[2k], T[2k + 1] of step k (T[0], T[1]: class bits), live beams A0,
 // A1.  The line word of step k is read once for both sectors (grid cells and
 // seen cells) and their new marks go out as one OR.
-template <typename WT, int KM>
-__device__ __forceinline__ void fan_pair(const State& s, const Lds<WT>& L, const uint32_t* T, int a,
+template <class CT, typename WT = typename CT::WT>
+__device__ __forceinline__ void fan_pair(const State& s, const CT& C, const uint32_t* T, int a,
                                          uint32_t A0, uint32_t A1, int kt) {
-  constexpr int SU = MC_FAN_SU;  // steps per batch: reads, then the live-beam chains, then marks
+  constexpr int KM = CT::KM, SU = MC_FAN_SU;  // SU steps per batch: reads, then the live-beam chains, then marks
+  const Lds<WT>& L = C.L;
   const uint32_t MD = (uint32_t)(row_plane_words(s.N, s.TW, (int)sizeof(WT)) * (int)sizeof(WT));  // neg -> marks
   const uint8_t* spread = reinterpret_cast<const uint8_t*>(L.fan);
   const uint8_t* expand = spread + 2048;
@@ -966,9 +1005,9 @@ __device__ __forceinline__ void fan_pair(const State& s, const Lds<WT>& L, const
   }
 }
 
-template <int NT, int EPW, typename WT, int KM>
-__device__ __forceinline__ void fan_march(const State& s, const Ctx<NT, EPW, WT>& C) {
-  constexpr int LPE = Ctx<NT, EPW, WT>::LPE;
+template <class CT, typename WT = typename CT::WT>
+__device__ __forceinline__ void fan_march(const State& s, const CT& C) {
+  constexpr int LPE = CT::LPE, KM = CT::KM;
   const Lds<WT>& L = C.L;
   const int N = s.N;
   const int kt = KM > 0 ? KM : s.fan_kt;
@@ -1004,7 +1043,7 @@ __device__ __forceinline__ void fan_march(const State& s, const Ctx<NT, EPW, WT>
         if (c0 >= (int)d[4] && c0 <= (int)d[5]) A[h] &= ~(1u << ((desc >> 3) & 7u));
       }
     }
-    fan_pair<WT, KM>(s, L, T, a, A[0], A[1], kt);
+    fan_pair(s, C, T, a, A[0], A[1], kt);
   }
   if (__ballot(exc)) {  // one-beam march of the left-out beams, from the start's bits
     if (exc) {
@@ -1019,16 +1058,14 @@ __device__ __forceinline__ void fan_march(const State& s, const Ctx<NT, EPW, WT>
         W[2 * k] = (uint32_t)(lo + 32) | (K >= k ? (1u << 16) : 0u);
         W[2 * k + 1] = 0u;
       }
-      fan_pair<WT, KM>(s, L, W, a, 1u, 0u, kt);
+      fan_pair(s, C, W, a, 1u, 0u, kt);
     }
   }
 }
 
-template <int NT, int EPW, typename WT, int SUK, int KN, int KM = 0, int RPLX = 0>
-__device__ __forceinline__ void sense(const State& s, const Ctx<NT, EPW, WT>& C) {
-  constexpr int LPE = Ctx<NT, EPW, WT>::LPE;
-  constexpr int RPL = RPLX > 0 ? RPLX : Ctx<NT, EPW, WT>::RPL;
-  constexpr int SU = SUK;
+template <class CT, typename WT = typename CT::WT>
+__device__ __forceinline__ void sense(const State& s, const CT& C) {
+  constexpr int LPE = CT::LPE, RPL = CT::RPL, SU = CT::SUK;
   const Lds<WT>& L = C.L;
   const int N = s.N, TW = s.TW, TW2 = TW * TW;
   if (s.sensor == 0) {
@@ -1048,7 +1085,7 @@ __device__ __forceinline__ void sense(const State& s, const Ctx<NT, EPW, WT>& C)
       if (b3) lds_or<WT>(&L.fpr[row_word<WT>(s, a, lx)], (WT)b3 << ly);
     }
     if (fan_on(s)) {
-      fan_march<NT, EPW, WT, KM>(s, C);
+      fan_march(s, C);
       return;
     }
     WT* sink = L.sink + (threadIdx.x & 63);
@@ -1100,8 +1137,7 @@ __device__ __forceinline__ void sense(const State& s, const Ctx<NT, EPW, WT>& C)
             for (int j = 0; j < RPL; ++j) {
               const bool dup = dense && prev_on && q[j].P == prev_p;
               prev_p = q[j].P;
-              prev_on = ray_mark<WT, KN>(L, q[j], k0 + u, nr[u][j], fr[u][j], sink_m, dup, dense,
-                                         k1 != 0 && k0 + u == 1);
+              prev_on = ray_mark(C, q[j], k0 + u, nr[u][j], fr[u][j], sink_m, dup, dense, k1 != 0 && k0 + u == 1);
               ray_advance(q[j], k0 + u);
             }
           }
@@ -1130,9 +1166,9 @@ __device__ __forceinline__ void sense(const State& s, const Ctx<NT, EPW, WT>& C)
 // lidar: mark rows -> mark tiles (after the march, before the merge)
 // The lane keeps its items' marks in registers for the merge; only the free
 // marks go to LDS (other lanes' union dedup reads them).
-template <int NT, int EPW, typename WT, int KI>
-__device__ __forceinline__ void gather_marks(const State& s, const Ctx<NT, EPW, WT>& C, Items<KI>& I) {
-  constexpr int LPE = Ctx<NT, EPW, WT>::LPE;
+template <class CT, typename WT = typename CT::WT>
+__device__ __forceinline__ void gather_marks(const State& s, const CT& C, Items<CT::KI>& I) {
+  constexpr int LPE = CT::LPE, KI = CT::KI;
   const Lds<WT>& L = C.L;
   const int TW = s.TW, TW2 = TW * TW;
   const int items = s.N * TW2;
@@ -1154,10 +1190,10 @@ __device__ __forceinline__ void gather_marks(const State& s, const Ctx<NT, EPW, 
 }
 
 // single_square_tool: only the robot's own cell becomes free (:233-234)
-template <int NT, int EPW, typename WT>
-__device__ __forceinline__ void single_tool(const State& s, const Ctx<NT, EPW, WT>& C) {
-  constexpr int LPE = Ctx<NT, EPW, WT>::LPE;
-  const Lds<WT>& L = C.L;
+template <class CT>
+__device__ __forceinline__ void single_tool(const State& s, const CT& C) {
+  constexpr int LPE = CT::LPE;
+  const Lds<typename CT::WT>& L = C.L;
   const int TW = s.TW, TW2 = TW * TW;
   for (int idx = C.sub; idx < s.N * TW2; idx += LPE) {
     const int a = udiv(idx, s.mg_TW2);
@@ -1178,10 +1214,10 @@ __device__ __forceinline__ void single_tool(const State& s, const Ctx<NT, EPW, W
 // marks_in_regs: the lidar's free marks are in I.mf (else L.fp: the square
 // sensor, or single_square_tool's own cell); obst_in_regs: its obstacle marks
 // are in I.mo (lidar, with or without single_square_tool; else L.op)
-template <int NT, int EPW, typename WT, int KI, int NS>
-__device__ __forceinline__ void merge(const State& s, const Ctx<NT, EPW, WT>& C, Items<KI>& I,
-                                      bool marks_in_regs, bool obst_in_regs) {
-  constexpr int LPE = Ctx<NT, EPW, WT>::LPE;
+template <class CT, typename WT = typename CT::WT>
+__device__ __forceinline__ void merge(const State& s, const CT& C, Items<CT::KI>& I, bool marks_in_regs,
+                                      bool obst_in_regs) {
+  constexpr int LPE = CT::LPE, EPW = CT::EPW, KI = CT::KI, NS = CT::NSM;
   const Lds<WT>& L = C.L;
   const int TW = s.TW;
   const int items = s.N * TW * TW;
@@ -1243,10 +1279,7 @@ __device__ __forceinline__ void merge(const State& s, const Ctx<NT, EPW, WT>& C,
     if (idx < items) {
       const uint64_t fp = marks_in_regs ? I.mf[k] : L.fp[idx];
       const uint64_t op = obst_in_regs ? I.mo[k] : L.op[idx];
-      uint64_t f0, o0, u0;
-      old_tiles<KI>(I, k, f0, o0, u0);  // first use of the mask loads
-      I.f[k] = f0;
-      I.o[k] = o0;
+      const uint64_t f0 = I.f[k], o0 = I.o[k], u0 = I.u[k];  // first use of the mask loads
       I.nf[k] = fp & ~f0;
       I.no[k] = op & ~o0;
       L.fold[idx] = f0 | fp;
@@ -1335,9 +1368,9 @@ __device__ __forceinline__ int row_dist(WT row, int c) {  // |c - nearest set bi
   return h;
 }
 
-template <int NT, int EPW, typename WT>
-__device__ __forceinline__ void dist_window(const State& s, const Ctx<NT, EPW, WT>& C, uint64_t skip) {
-  constexpr int LPE = Ctx<NT, EPW, WT>::LPE;
+template <class CT, typename WT = typename CT::WT>
+__device__ __forceinline__ void dist_window(const State& s, const CT& C, uint64_t skip) {
+  constexpr int LPE = CT::LPE;
   const Lds<WT>& L = C.L;
   const int N = s.N, E = s.E, T = 5 + E * E, RB = 8 * s.TW;
   const WT cols = sizeof(WT) == 8 && RB >= 64 ? ~(WT)0 : (WT)(((uint64_t)1 << RB) - 1);  // the block's columns
@@ -1384,10 +1417,9 @@ __device__ __forceinline__ void dist_window(const State& s, const Ctx<NT, EPW, W
 // a0 + l / 32 in pass a0, so a lane's target offsets are computed once for
 // every pass (no per-item division into (agent, target) and (row, column)),
 // and an agent's skip / M test is uniform over its 32 lanes.
-template <int NT, int EPW, typename WT>
-__device__ __forceinline__ void dist_window_am(const State& s, const Ctx<NT, EPW, WT>& C, uint64_t skip) {
-  constexpr int LPE = Ctx<NT, EPW, WT>::LPE;
-  constexpr int APP = LPE / 32;  // agents per pass
+template <class CT, typename WT = typename CT::WT>
+__device__ __forceinline__ void dist_window_am(const State& s, const CT& C, uint64_t skip) {
+  constexpr int LPE = CT::LPE, APP = LPE / 32;  // APP: agents per pass
   const Lds<WT>& L = C.L;
   const int N = s.N, E = s.E, T = 5 + E * E, RB = 8 * s.TW;
   const WT cols = sizeof(WT) == 8 && RB >= 64 ? ~(WT)0 : (WT)(((uint64_t)1 << RB) - 1);  // the block's columns
@@ -1430,14 +1462,14 @@ __device__ __forceinline__ void dist_window_am(const State& s, const Ctx<NT, EPW
   }
 }
 
-// dist_window_am with the agent count known at compile time (NS): the passes'
+// dist_window_am with the agent count known at compile time (NS = SH::N): the passes'
 // first row reads (the target's own row: the common answer) are issued
 // together, then the few lanes whose target is not covered scan outward,
 // then the stores -- one LDS latency chain for all passes instead of one per
 // pass
-template <int NT, int EPW, typename WT, int NS>
-__device__ __forceinline__ void dist_window_am2(const State& s, const Ctx<NT, EPW, WT>& C, uint64_t skip) {
-  constexpr int LPE = Ctx<NT, EPW, WT>::LPE;
+template <class CT, typename WT = typename CT::WT>
+__device__ __forceinline__ void dist_window_am2(const State& s, const CT& C, uint64_t skip) {
+  constexpr int LPE = CT::LPE, NS = CT::SH::N;
   constexpr int APP = LPE / 32;               // agents per pass
   constexpr int NP = (NS + APP - 1) / APP;    // passes
   const Lds<WT>& L = C.L;
@@ -1507,9 +1539,10 @@ __device__ __forceinline__ void st_tile(uint64_t* base, uint32_t idx, uint64_t v
   else base[idx] = v;
 }
 
-template <int NT, int EPW, typename WT, int KI, bool O32 = false>
-__device__ __forceinline__ void store_tiles(const State& s, const Ctx<NT, EPW, WT>& C,
-                                            const Items<KI>& I) {
+template <class CT>
+__device__ __forceinline__ void store_tiles(const State& s, const CT& C, const Items<CT::KI>& I) {
+  constexpr int KI = CT::KI;
+  constexpr bool O32 = CT::O32;
   const uint32_t mt = (uint32_t)s.MT;
 #pragma unroll
   for (int k = 0; k < KI; ++k) {
@@ -1564,24 +1597,32 @@ __device__ __forceinline__ void reload_state(State& s, EnvIO& io) {
   }
 }
 
+// a sentinel's done ends the episode (utils.py:22,41): its record, from the env's counters fc, cs before the step
+__device__ __forceinline__ void sentinel_done(const State& s, const EnvIO& io, int e, int g, uint32_t fc, int cs) {
+  io.reward_out[e] = 0.0;
+  io.done_out[e] = 1;
+  s.ep_pc[e] = (double)fc / (double)s.numfree[g];
+  s.ep_len[e] = cs;
+}
+
 // sense -> (lidar: gather) -> (single tool) -> merge, with the barriers
-template <int NT, int EPW, typename WT, int KI, int SUK, int NS, int KN, int KM = 0, int RPLX = 0>
-__device__ __forceinline__ void sense_and_merge(const State& s0, const Ctx<NT, EPW, WT>& C,
-                                                Items<KI>& I) {
+template <class CT>
+__device__ __forceinline__ void sense_and_merge(const State& s0, const CT& C, Items<CT::KI>& I) {
+  [[maybe_unused]] constexpr int EPW = CT::EPW;  // STAMP
   State s = s0;
-  if (MC_ABL != 5) sense<NT, EPW, WT, SUK, KN, KM, RPLX>(s, C);
+  if (MC_ABL != 5) sense(s, C);
   __syncthreads();
   STAMP(13);
   if (s.sensor == 0) {
-    gather_marks<NT, EPW, WT, KI>(s, C, I);
+    gather_marks(s, C, I);
     __syncthreads();
   }
   STAMP(4);
   if (s.sst) {
-    single_tool<NT, EPW, WT>(s, C);
+    single_tool(s, C);
     __syncthreads();
   }
-  merge<NT, EPW, WT, KI, NS>(s, C, I, s.sensor == 0 && !s.sst, s.sensor == 0);
+  merge(s, C, I, s.sensor == 0 && !s.sst, s.sensor == 0);
 }
 
 // --------------------------------------------------------------------------
@@ -1598,11 +1639,9 @@ __device__ __forceinline__ void set_agent(const State& s, const Lds<WT>& L, int 
   L.by[a] = (y - s.H - 1) >> 3;
 }
 
-template <int NT, int EPW, typename WT, int SUK, int NS, int KN, bool O32, int KM = 0, int RPLX = 0>
-__device__ __forceinline__ void reset_env(const State& s, const Ctx<NT, EPW, WT>& C,
-                                          const int32_t* inj_pos) {
-  constexpr int LPE = Ctx<NT, EPW, WT>::LPE;
-  constexpr int KI = Ctx<NT, EPW, WT>::KI;
+template <class CT, typename WT = typename CT::WT>
+__device__ __forceinline__ void reset_env(const State& s, const CT& C, const int32_t* inj_pos) {
+  constexpr int LPE = CT::LPE, KI = CT::KI;
   const Lds<WT>& L = C.L;
   const int N = s.N;
   const int e = C.e;
@@ -1672,11 +1711,11 @@ __device__ __forceinline__ void reset_env(const State& s, const Ctx<NT, EPW, WT>
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   Items<KI> I;
-  zero_marks<NT, EPW, WT>(s, C);
-  stage<NT, EPW, WT, KI, O32>(s, C, g, /*load_masks=*/false, I);
+  zero_marks(s, C);
+  stage(s, C, g, /*load_masks=*/false, I);
   __syncthreads();
-  sense_and_merge<NT, EPW, WT, KI, SUK, NS, KN, KM, RPLX>(s, C, I);
-  store_tiles<NT, EPW, WT, KI, O32>(s, C, I);
+  sense_and_merge(s, C, I);
+  store_tiles(s, C, I);
   __syncthreads();
   if (C.sub == 0) {
     s.rec[e].free_cnt = L.sc->cnt_free;
@@ -1743,10 +1782,9 @@ __device__ __forceinline__ uint64_t obs_row(const State& s, const Lds<WT>& L, co
   return (acc >> (ly0 & 7)) & low_mask(E);
 }
 
-template <int NT, int EPW, typename WT, int NS>
-__device__ __forceinline__ void write_obs(const State& s, const Ctx<NT, EPW, WT>& C,
-                                          uint8_t* obs_out) {
-  constexpr int LPE = Ctx<NT, EPW, WT>::LPE;
+template <class CT, typename WT = typename CT::WT>
+__device__ __forceinline__ void write_obs(const State& s, const CT& C, uint8_t* obs_out) {
+  constexpr int LPE = CT::LPE, NS = CT::NS_OBS;
   const Lds<WT>& L = C.L;
   const int E = s.E;
   const int rows = s.N * s.Lc * E;
@@ -1795,18 +1833,11 @@ __device__ __forceinline__ void write_obs(const State& s, const Ctx<NT, EPW, WT>
 // writes dwords l, l + 64, ...; dword d is the nibble at bit 4d of the
 // slot's crop stream (fetched from the crop lanes by ds_bpermute), spread to
 // bytes by one multiply.  No per-row or per-layer branches.
-template <int EGO, int NS, int LC = 3>
-struct ObsFast {
-  static constexpr int E = 2 * EGO + 1, EE = E * E, NB = LC * NS;
-  static constexpr bool ok = EGO > 0 && NS > 0 && EE <= 28 && (NB * EE) % 4 == 0 &&
-                             (LC == 3 || LC == 4);
-};
-
-template <int NT, int EPW, typename WT, int NS, int EGO, int LC = 3>
-__device__ __forceinline__ void write_obs_fast(const State& s, const Ctx<NT, EPW, WT>& C,
-                                               uint8_t* obs_out) {
+template <class CT, typename WT = typename CT::WT>
+__device__ __forceinline__ void write_obs_fast(const State& s, const CT& C, uint8_t* obs_out) {
+  constexpr int NT = CT::NT, EPW = CT::EPW, LPE = CT::LPE;
+  constexpr int NS = CT::SH::N, EGO = CT::SH::EGO, LC = CT::SH::LC;
   using OF = ObsFast<EGO, NS, LC>;
-  constexpr int LPE = Ctx<NT, EPW, WT>::LPE;
   constexpr int E = OF::E, EE = OF::EE, NB = OF::NB;
   static_assert(NB <= LPE && NB <= 64, "one crop per lane of the first wave");
   static_assert(NT == 64 || EPW == 1, "one wave, or one env per workgroup");
@@ -1939,35 +1970,13 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
   specialize<SH>(s);
   EnvIO io = args.io;
   const int mode = io.mode;
-  using CtxT = Ctx<NT, EPW, WT>;
-  constexpr int LPE = CtxT::LPE;
-  constexpr int KI = CtxT::KI;
-  // march steps per batch: the whole march when the shape fixes a short
-  // beam_kmax, a quarter of a long one (register pressure)
-  constexpr int SUK0 = (SH::KM > 0 && SH::KM <= 12) ? SH::KM : (SH::KM > 12 ? (SH::KM + 3) / 4 : 8);
-  constexpr int NSM = (SH::N > 0 && SH::N <= 8) ? SH::N : 0;  // compile-time agent count, if small
-  // rays per lane per march pass: 3 where that saves a pass over the
-  // default (C5: 336 rays over 128 lanes, one pass of 3 instead of two of 2)
-  constexpr int RPLK = SH::N > 0 && SH::NB > 0 && SH::NB < 64 && EPW == 1 &&
-                               (SH::N * SH::NB + 3 * NT - 1) / (3 * NT) < (SH::N * SH::NB + CtxT::RPL * NT - 1) / (CtxT::RPL * NT)
-                           ? 3
-                           : 0;
-  // (3 rays per lane: half the march's batch, the row words of a batch stay
-  // within the register budget)
-  constexpr int SUK = RPLK == 3 ? (SUK0 + 1) / 2 : SUK0;
-  // compiled shapes with up to 8 agents: map byte offsets fit 32 bits
-  // (launch_env checks; the C5 shape's maps pass 4 GB)
-  constexpr bool O32 = SH::N > 0 && SH::N <= 8;
-  // register front (front_regs / moves_front): compiled agent count <= 8,
-  // one wave per workgroup
-  constexpr bool FRONT = NSM > 0 && NT == 64;
-  // moves from registers in the first wave of a multi-wave env during round
-  // trip 2 (compiled agent count <= 8, lidar: C4)
-  constexpr bool EARLY = NSM > 0 && NT > 64 && EPW == 1 && SH::NB > 0;
+  using CT = Ctx<NT, EPW, WT, SH>;  // the instantiation's compile-time configuration (see Ctx)
+  constexpr int LPE = CT::LPE, KI = CT::KI, NSM = CT::NSM;
+  constexpr bool O32 = CT::O32, FRONT = CT::FRONT, EARLY = CT::EARLY, kPrePrefetch = CT::kPrePrefetch;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int N = s.N;
-  CtxT C;
+  CT C;
   const int slot = EPW == 1 ? 0 : tid / LPE;
   C.sub = EPW == 1 ? tid : tid - slot * LPE;
   C.lane0 = EPW == 1 ? 0 : slot * LPE;
@@ -2027,7 +2036,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
     chd = hp[0];
     chb = *reinterpret_cast<const int2*>(hp + 1);
   }
-  zero_marks<NT, EPW, WT>(s, C);  // overlaps the round trip
+  zero_marks(s, C);  // overlaps the round trip
   // every result is needed below: keep the compiler from sinking a load into
   // the branch that uses it (that would make it a round trip of its own)
   asm volatile("" ::"v"(p0.x), "v"(p0.y), "v"(act_raw), "v"(act0_raw), "v"(req_raw), "v"(g0),
@@ -2091,16 +2100,16 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
       // (the moves wait only for them), then every staged tile; block
       // origins and moves from registers (front_regs)
       Front<NSM> F;
-      front_regs<NT, EPW, WT, NSM>(s, C, p0.x, p0.y, act, F);
+      front_regs(s, C, p0.x, p0.y, act, F);
       const int dx = (act == 0) - (act == 2), dy = (act == 1) - (act == 3);
       const int tx = p0.x + dx, ty = p0.y + dy;
       const bool inb = (unsigned)tx < (unsigned)s.Wp && (unsigned)ty < (unsigned)s.Lp;
       const uint64_t tt = ld_tile<O32>(s.grid_neg, __umul24((uint32_t)g0, (uint32_t)s.MT) +
                                                        tile_index24(s.TCS, inb ? tx >> 3 : 0, inb ? ty >> 3 : 0));
-      stage_load<NT, EPW, WT, KI, O32, NSM>(s, C, g0, true, I, &F);
-      moves_front<NT, EPW, WT, NSM>(s, C, F, !inb || ((tt >> tile_bit(tx, ty)) & 1ull),
-                                    (uint32_t)tx | ((uint32_t)ty << 16), act, moved0, -s.pen);
-      stage_scatter<NT, EPW, WT, KI>(s, C, I);
+      stage_load(s, C, g0, true, I, &F);
+      moves_front(s, C, F, !inb || ((tt >> tile_bit(tx, ty)) & 1ull), (uint32_t)tx | ((uint32_t)ty << 16), act,
+                  moved0, -s.pen);
+      stage_scatter(s, C, I);
     } else if constexpr (EARLY) {
       // ---- round trip 2 with the moves of a multi-wave env: the first wave
       // moves the robots from registers (front_regs / moves_front: lane i
@@ -2111,17 +2120,17 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
       const bool inb = (unsigned)tx < (unsigned)s.Wp && (unsigned)ty < (unsigned)s.Lp;
       const uint64_t tt = ld_tile<O32>(s.grid_neg, __umul24((uint32_t)g0, (uint32_t)s.MT) +
                                                        tile_index24(s.TCS, inb ? tx >> 3 : 0, inb ? ty >> 3 : 0));
-      stage_load<NT, EPW, WT, KI, O32>(s, C, g0, true, I);
+      stage_load(s, C, g0, true, I);
       STAMP(15);  // loads issued (the first wave's moves follow)
       if (C.sub < 64) {
         Front<NSM> F;
-        front_regs<NT, EPW, WT, NSM>(s, C, p0.x, p0.y, act, F);
-        moves_front<NT, EPW, WT, NSM>(s, C, F, !inb || ((tt >> tile_bit(tx, ty)) & 1ull),
-                                      (uint32_t)tx | ((uint32_t)ty << 16), act, moved0, -s.pen);
+        front_regs(s, C, p0.x, p0.y, act, F);
+        moves_front(s, C, F, !inb || ((tt >> tile_bit(tx, ty)) & 1ull), (uint32_t)tx | ((uint32_t)ty << 16), act,
+                    moved0, -s.pen);
       }
-      stage_scatter<NT, EPW, WT, KI>(s, C, I);
+      stage_scatter(s, C, I);
     } else {
-      stage<NT, EPW, WT, KI, O32>(s, C, g0, true, I);  // ---- round trip 2 ----
+      stage(s, C, g0, true, I);  // ---- round trip 2 ----
     }
     // count_nonzero(grid > 0) for percent_covered: kept in a register until
     // the reward (no wait here)
@@ -2139,11 +2148,11 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
       // the loop on the scalar unit from v_readlane copies, 111.3 vs 107.8 us
       // per env kernel, profiles/r4/c5_grid/)
       if constexpr (SH::N > 0 && SH::N <= 8) {
-        if (NT == 64 || C.sub < 64) moves_regs<NT, EPW, WT, SH::N>(s, C, -s.pen);
+        if (NT == 64 || C.sub < 64) moves_regs(s, C, -s.pen);
       } else if constexpr (SH::N > 8 && EPW == 1) {
-        if (C.sub < 64) moves_par<NT, EPW, WT, SH::N>(s, C, -s.pen);
+        if (C.sub < 64) moves_par(s, C, -s.pen);
       } else if (C.sub < 64) {
-        moves<NT, EPW, WT>(s, C, -s.pen);
+        moves(s, C, -s.pen);
       }
       __syncthreads();
     }
@@ -2151,10 +2160,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
     reload_state<SH, EPW>(s, io);
     // dist_reward: lane i < N loads its agent's PRE terms (the last step's
     // dist kernels wrote them) now that its move is known; they land during
-    // the sensing
-    // (compiled shapes; the generic kernels keep the loads in the reward:
-    // two more live registers there cost the u64 ones a wave per SIMD)
-    constexpr bool kPrePrefetch = SH::N > 0;
+    // the sensing (kPrePrefetch: compiled shapes)
     // one env per workgroup: the env's counters re-read here (they land
     // during the sensing) rather than kept from round trip 1 in SGPRs,
     // which spilled (nothing writes them before the reward)
@@ -2176,7 +2182,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
       dpre0 = pr[0];
       dprek = pr[1 + k];
     }
-    sense_and_merge<NT, EPW, WT, KI, SUK, NSM, SH::KN, SH::KM, RPLK>(s, C, I);
+    sense_and_merge(s, C, I);
     __syncthreads();
     STAMP(5);
     reload_state<SH, EPW>(s, io);
@@ -2250,16 +2256,16 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
         // (tried, round 5: one lane per (agent, target row) growing the
         // row's covered set by a bit-parallel dilation -- 83.6 against 81.7
         // us at the C5 steady state, profiles/r5/win/; removed)
-        if constexpr (Ctx<NT, EPW, WT>::LPE % 32 == 0) {
+        if constexpr (LPE % 32 == 0) {
           if constexpr (SH::N > 0 && SH::N <= 64) {
-            if (5 + s.E * s.E <= 32) dist_window_am2<NT, EPW, WT, SH::N>(s, C, skip);
-            else dist_window<NT, EPW, WT>(s, C, skip);
+            if (5 + s.E * s.E <= 32) dist_window_am2(s, C, skip);
+            else dist_window(s, C, skip);
           } else {
-            if (5 + s.E * s.E <= 32) dist_window_am<NT, EPW, WT>(s, C, skip);
-            else dist_window<NT, EPW, WT>(s, C, skip);
+            if (5 + s.E * s.E <= 32) dist_window_am(s, C, skip);
+            else dist_window(s, C, skip);
           }
         } else {
-          dist_window<NT, EPW, WT>(s, C, skip);
+          dist_window(s, C, skip);
         }
       }
       __syncthreads();
@@ -2271,20 +2277,15 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
     STAMP(6);
     reload_state<SH, EPW>(s, io);
     if (!do_reset) {
-      store_tiles<NT, EPW, WT, KI, O32>(s, C, I);
+      store_tiles(s, C, I);
       STAMP(7);
     } else {
-      reset_env<NT, EPW, WT, SUK, NSM, SH::KN, O32, SH::KM, RPLK>(s, C, nullptr);  // the finished episode's tiles are not stored
+      reset_env(s, C, nullptr);  // the finished episode's tiles are not stored
     }
   } else if (reset_req || sent_reset) {
     reload_state<SH, EPW>(s, io);
-    if (C.sub == 0 && sentinel) {  // the sentinel's done ends the episode (utils.py:22,41)
-      io.reward_out[e] = 0.0;
-      io.done_out[e] = 1;
-      s.ep_pc[e] = (double)free_old / (double)s.numfree[g0];
-      s.ep_len[e] = currstep0;
-    }
-    reset_env<NT, EPW, WT, SUK, NSM, SH::KN, O32, SH::KM, RPLK>(s, C, reset_req ? io.inj_pos : nullptr);
+    if (C.sub == 0 && sentinel) sentinel_done(s, io, e, g0, free_old, currstep0);
+    reset_env(s, C, reset_req ? io.inj_pos : nullptr);
     dlist = s.dist && C.sub < N;  // fresh maps: M unknown
   } else {
     // sentinel step without auto-reset / env left out of a partial reset:
@@ -2295,17 +2296,12 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
     // race with another wave's stage_fold stores.
     reload_state<SH, EPW>(s, io);
     Items<KI> I;
-    stage_load<NT, EPW, WT, KI, O32>(s, C, g0, true, I);
-    stage_fold<NT, EPW, WT, KI>(s, C, I);
+    stage_load(s, C, g0, true, I);
+    stage_fold(s, C, I);
     // unchanged maps keep their dist terms; an unknown M (a state upload)
     // needs the full transform
     dlist = s.dist && C.sub < N && L.dm[C.sub] < 0;
-    if (C.sub == 0 && sentinel) {
-      io.reward_out[e] = 0.0;
-      io.done_out[e] = 1;
-      s.ep_pc[e] = (double)free_old / (double)s.numfree[g0];
-      s.ep_len[e] = currstep0;
-    }
+    if (C.sub == 0 && sentinel) sentinel_done(s, io, e, g0, free_old, currstep0);
   }
   __syncthreads();
 
@@ -2366,11 +2362,10 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
   }
   STAMP(8);
   reload_state<SH, EPW>(s, io);
-  if constexpr (ObsFast<SH::EGO, SH::N, SH::LC>::ok && (NT == 64 || EPW == 1) &&
-                ObsFast<SH::EGO, SH::N, SH::LC>::NB <= 64) {
-    if (MC_ABL != 4) write_obs_fast<NT, EPW, WT, SH::N, SH::EGO, SH::LC>(s, C, io.obs_out);  // every lane of the workgroup
+  if constexpr (CT::OBS_FAST) {
+    if (MC_ABL != 4) write_obs_fast(s, C, io.obs_out);  // every lane of the workgroup
   } else {
-    if (valid) write_obs<NT, EPW, WT, (SH::N > 0 && SH::N <= 16) ? SH::N : 0>(s, C, io.obs_out);
+    if (valid) write_obs(s, C, io.obs_out);
   }
   STAMP(9);
   if (valid && io.adj_out != nullptr) {  // updateCommmunicationGraph (:374-391)
@@ -2441,6 +2436,20 @@ using ShapeC5 = Shape<16, 10, 21, 2, 10, 8, 4, 1>;  // 16 agents
 #define MC_EL(T, P, W, SH, NAME) \
   EnvLaunch { "env_kernel<" #T "," #P "," NAME ">", &launch_one<T, P, W, SH> }
 
+// the generic (runtime-shape) kernel of nt lanes, one env per workgroup
+template <typename W>
+static EnvLaunch generic_env(int nt) {
+#define MC_GEN(T) (sizeof(W) == 4 ? MC_EL(T, 1, W, Dynamic, "u32,generic") : MC_EL(T, 1, W, Dynamic, "u64,generic"))
+  switch (nt) {
+    case 64: return MC_GEN(64);
+    case 128: return MC_GEN(128);
+    case 256: return MC_GEN(256);
+    case 512: return MC_GEN(512);
+    default: return MC_GEN(1024);
+  }
+#undef MC_GEN
+}
+
 // The instantiation for this state: compiled shapes when the runtime State
 // matches one exactly (and its map offsets fit 32 bits), else the generic
 // kernel for the lane count / envs per workgroup.
@@ -2462,24 +2471,12 @@ EnvLaunch select_env(const State& s, int nt, int epw) {
     if (nt == 64 && fits32 && spec && ShapeC2D::matches(s)) return MC_EL(64, 1, uint32_t, ShapeC2D, "u32,C2D");
     if (nt == 128 && spec && ShapeC5B::matches(s)) return MC_EL(128, 1, uint32_t, ShapeC5B, "u32,C5");
     if (nt == 128 && spec && ShapeC5::matches(s)) return MC_EL(128, 1, uint32_t, ShapeC5, "u32,C5");
-    switch (nt) {
-      case 64: return MC_EL(64, 1, uint32_t, Dynamic, "u32,generic");
-      case 128: return MC_EL(128, 1, uint32_t, Dynamic, "u32,generic");
-      case 256: return MC_EL(256, 1, uint32_t, Dynamic, "u32,generic");
-      case 512: return MC_EL(512, 1, uint32_t, Dynamic, "u32,generic");
-      default: return MC_EL(1024, 1, uint32_t, Dynamic, "u32,generic");
-    }
+    return generic_env<uint32_t>(nt);
   }
   if (nt == 256 && fits32 && spec && ShapeC4B::matches(s)) return MC_EL(256, 1, uint64_t, ShapeC4B, "u64,C4");
   if (nt == 256 && fits32 && spec && ShapeC4::matches(s)) return MC_EL(256, 1, uint64_t, ShapeC4, "u64,C4");
   if (nt == 256 && fits32 && spec && ShapeC4R::matches(s)) return MC_EL(256, 1, uint64_t, ShapeC4R, "u64,C4");
-  switch (nt) {
-    case 64: return MC_EL(64, 1, uint64_t, Dynamic, "u64,generic");
-    case 128: return MC_EL(128, 1, uint64_t, Dynamic, "u64,generic");
-    case 256: return MC_EL(256, 1, uint64_t, Dynamic, "u64,generic");
-    case 512: return MC_EL(512, 1, uint64_t, Dynamic, "u64,generic");
-    default: return MC_EL(1024, 1, uint64_t, Dynamic, "u64,generic");
-  }
+  return generic_env<uint64_t>(nt);
 }
 #undef MC_EL
 
