@@ -92,6 +92,8 @@ struct Env {
   void* bits_buf = nullptr;   // u64 [beam_count][max(Wp, Lp)]
   void* fan_buf = nullptr;    // u32 [State::fan_words]: fan march data (dense beam sets)
   size_t fan_cap = 0;         // words allocated in fan_buf
+  void* rayprog_buf = nullptr;  // u32: the ray programs (State::ray_prog; common beam patterns)
+  size_t rayprog_cap = 0;       // words allocated in rayprog_buf
   int beam_count = 0;
   bool grids_set = false;
   std::vector<void*> allocs;
@@ -526,6 +528,7 @@ void mc_destroy(void* env) {
   if (E->beams_buf) (void)hipFree(E->beams_buf);
   if (E->bits_buf) (void)hipFree(E->bits_buf);
   if (E->fan_buf) (void)hipFree(E->fan_buf);
+  if (E->rayprog_buf) (void)hipFree(E->rayprog_buf);
   delete E;
 }
 
@@ -775,6 +778,7 @@ int mc_set_beam_table(void* env, const double* host_table, int32_t num_beams) {
   E->beams_set = false;
   E->s.fan_nsec = E->s.fan_nspec = E->s.fan_kt = E->s.fan_words = 0;
   E->s.fan_data = nullptr;
+  E->s.ray_prog = nullptr;
   if (num_beams != E->beam_count || !E->beams_buf) {
     // the reference lets callers swap _thetalist after construction
     // (even beam counts): (re-)size the device tables
@@ -811,6 +815,24 @@ int mc_set_beam_table(void* env, const double* host_table, int32_t num_beams) {
     k1 |= 1u << (3 * (dx + 1) + (dy + 1));
   }
   E->s.beam_k1 = E->s.beam_common && !getenv("MARLCOV_NO_K1") ? k1 : 0u;
+  // ray programs of the launch geometry (set_launch_shape above, or
+  // mc_create's: only a new beam count changes it), for common patterns
+  if (E->s.beam_common) {
+    std::vector<uint32_t> rp;
+    const int epw = launch_epw(E);
+    if (mc::build_ray_prog(bt, E->s.N, mc::ray_lpe(E->nt, epw), mc::ray_rpl(E->nt, epw, E->s.N, num_beams), kmax,
+                           E->s.TW <= 4 ? 4 : 8, rp)) {
+      if (rp.size() > E->rayprog_cap) {
+        if (E->rayprog_buf) (void)hipFree(E->rayprog_buf);
+        E->rayprog_buf = nullptr;
+        E->rayprog_cap = 0;
+        HIP_TRY(hipMalloc(&E->rayprog_buf, rp.size() * 4));
+        E->rayprog_cap = rp.size();
+      }
+      HIP_TRY(hipMemcpy(E->rayprog_buf, rp.data(), rp.size() * 4, hipMemcpyHostToDevice));
+      E->s.ray_prog = (const uint32_t*)E->rayprog_buf;
+    }
+  }
   // fan march of a dense set (after nt / epw: they bound the special lanes);
   // MARLCOV_FAN=0 or MARLCOV_BEAM_TABLE keep the ray march (parity A/B)
   {

@@ -189,7 +189,7 @@ struct Ctx {
   static constexpr int NT = NT_, EPW = EPW_;      // workgroup lanes, envs per workgroup
   static constexpr int LPE = NT / EPW;            // lanes per env
   static constexpr int KI = kMaxItemsPerLane;     // staged tiles per lane
-  static constexpr int RPL0 = EPW == 1 ? 2 : 3;  // beams per lane per pass (C4 A/B: 3, 4 or 6 are slower)
+  static constexpr int RPL0 = ray_rpl0(EPW);      // beams per lane per pass (mc_internal.h)
   static constexpr int KM = SH::KM, KN = SH::KN;  // the shape's beam_kmax (fan trip count) and beam_kmin; 0: runtime
   // march steps per batch: the whole march when the shape fixes a short
   // beam_kmax, a quarter of a long one (register pressure)
@@ -199,11 +199,8 @@ struct Ctx {
   static constexpr int NSM = (SH::N > 0 && SH::N <= 8) ? SH::N : 0;
   // rays per lane per march pass: 3 where that saves a pass over the
   // default (C5: 336 rays over 128 lanes, one pass of 3 instead of two of 2)
-  static constexpr int RPLK = SH::N > 0 && SH::NB > 0 && SH::NB < 64 && EPW == 1 &&
-                                      (SH::N * SH::NB + 3 * NT - 1) / (3 * NT) < (SH::N * SH::NB + RPL0 * NT - 1) / (RPL0 * NT)
-                                  ? 3
-                                  : 0;
-  static constexpr int RPL = RPLK > 0 ? RPLK : RPL0;
+  static constexpr int RPLK = ray_rplk(NT, EPW, SH::N, SH::NB);
+  static constexpr int RPL = ray_rpl(NT, EPW, SH::N, SH::NB);
   // (3 rays per lane: half the march's batch, the row words of a batch stay
   // within the register budget)
   static constexpr int SUK = RPLK == 3 ? (SUK0 + 1) / 2 : SUK0;
@@ -224,6 +221,15 @@ struct Ctx {
   static constexpr bool OBS_FAST = ObsFast<SH::EGO, SH::N, SH::LC>::ok && (NT == 64 || EPW == 1) &&
                                    ObsFast<SH::EGO, SH::N, SH::LC>::NB <= 64;
   static constexpr int NS_OBS = (SH::N > 0 && SH::N <= 16) ? SH::N : 0;
+  // the march from the host-built ray programs (mc_internal.h build_ray_prog;
+  // select_env: State::ray_prog is set): compiled sparse-beam shapes of up to
+  // 8 agents with one wave per workgroup whose rays take one pass -- no beam
+  // records in LDS, no ray_init, no ray_advance chain
+  static constexpr bool RAYPROG = SH::NB > 0 && SH::NB < 64 && SH::KM > 0 && SH::KM <= 12 && NT == 64 && NSM > 0 &&
+                                  sizeof(WT) == 4 && SH::N * SH::NB <= RPL * LPE;
+  static constexpr int RPW = RAYPROG ? ray_prog_row_words(RPL, SH::KM) : 4;  // words of a lane's program row
+  static_assert(!RAYPROG || ray_prog_span(SH::N, (int)sizeof(WT), SH::KM) <= 32767, "ray program offsets are int16");
+  uint32_t rp[RPW];  // RAYPROG: this lane's program row (round trip 1)
   int sub;    // lane within the env
   int lane0;  // first lane of this env's slot within the wave
   int e;      // env index
@@ -750,6 +756,22 @@ __device__ __forceinline__ void moves_regs(const State& s, const CT& C, double p
   }
 }
 
+typedef __attribute__((address_space(3))) char lds_char;
+
+// Ray programs (Ctx::RAYPROG; the march below).  P0[a]: agent a's post-move
+// cell packed like Ray::P, one LDS word per agent in the place of the beam
+// records (which these shapes do not stage); published with the post-move
+// cells (moves_front, reset_env), read by the lanes whose rays belong to the
+// agent.
+template <typename WT>
+__device__ __forceinline__ uint32_t* ray_p0_words(const Lds<WT>& L) { return reinterpret_cast<uint32_t*>(L.beams); }
+// (the same expression as ray_init's R.P; bx, by: the agent's block origin)
+template <typename WT>
+__device__ __forceinline__ uint32_t ray_p0(const State& s, const Lds<WT>& L, int a, int x, int y, int bx, int by) {
+  const uint32_t plane = (uint32_t)(uintptr_t)(const lds_char*)(const char*)L.negr;
+  return ((plane + (uint32_t)row_word<WT>(s, a, x - 8 * bx) * (uint32_t)sizeof(WT)) << 6) | (uint32_t)(y - 8 * by);
+}
+
 // Moves from registers (Front): robot i's target-cell bit (grid < 0 or out of
 // bounds) was loaded by lane lane0 + i next to round trip 2 and is shared by
 // a ballot; every lane of the slot replays the robot-order loop; lane 0
@@ -798,6 +820,8 @@ __device__ __forceinline__ void moves_front(const State& s, const CT& C, const F
     for (int i = 0; i < NS; ++i) {
       L.x[i] = (int)(XY[i] & 0xFFFFu);
       L.y[i] = (int)(XY[i] >> 16);
+      if constexpr (CT::RAYPROG)
+        ray_p0_words(L)[i] = ray_p0(s, L, i, (int)(XY[i] & 0xFFFFu), (int)(XY[i] >> 16), F.bx[i], F.by[i]);
     }
     L.sc->pen = pen;
     L.sc->moved = moved;
@@ -814,8 +838,6 @@ __device__ __forceinline__ void moves_front(const State& s, const CT& C, const F
 // (mc_set_beam_table rejects K > H).  Row planes: the cell's word is one add,
 // its bit one shift.
 // --------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) char lds_char;
-
 // A ray's cell is packed as P = (row word's LDS address << 6) | column: one
 // add advances it, P >> 6 addresses the row word, and the shift amount of
 // 1 << P is taken mod the word width by the hardware.
@@ -865,6 +887,33 @@ template <typename WT>
 __device__ __forceinline__ const WT* ray_word(const Lds<WT>& L, const WT* plane, const Ray& R) {
   const lds_char* p = (const lds_char*)(uintptr_t)(R.P >> 6) + (plane - L.negr) * (int)sizeof(WT);
   return reinterpret_cast<const WT*>((const char*)p);
+}
+
+// Ray programs (Ctx::RAYPROG): this lane's row, RPW / 4 16-byte loads (quad
+// q of the slot's lanes is consecutive memory: ray_prog_word), unconditional
+// (the table has a row for every lane of a slot)
+template <class CT>
+__device__ __forceinline__ void load_ray_prog(const State& s, CT& C) {
+  const int4* src = reinterpret_cast<const int4*>(s.ray_prog) + C.sub;
+#pragma unroll
+  for (int q = 0; q < CT::RPW / 4; ++q) {
+    const int4 v = src[q * CT::LPE];
+    C.rp[4 * q] = (uint32_t)v.x;
+    C.rp[4 * q + 1] = (uint32_t)v.y;
+    C.rp[4 * q + 2] = (uint32_t)v.z;
+    C.rp[4 * q + 3] = (uint32_t)v.w;
+  }
+}
+// C with its program row loaded anew (a copy); C itself without programs
+template <class CT>
+__device__ __forceinline__ decltype(auto) with_ray_prog(const State& s, const CT& C) {
+  if constexpr (CT::RAYPROG) {
+    CT c = C;
+    load_ray_prog(s, c);
+    return c;
+  } else {
+    return (C);
+  }
 }
 
 // Branch-free mark: every lane issues one ds_or per ray and step; a lane with
@@ -1091,6 +1140,47 @@ __device__ __forceinline__ void sense(const State& s, const CT& C) {
     WT* sink = L.sink + (threadIdx.x & 63);
     const uint32_t sink_m = (uint32_t)(uintptr_t)(const lds_char*)(const char*)sink -
                             (uint32_t)((L.fpr - L.negr) * (int)sizeof(WT));
+    if constexpr (CT::RAYPROG) {
+      // the lane's rays from its program row (C.rp: build_ray_prog): the
+      // cell of ray j at step k is its agent's P0 plus a 16-bit offset -- one
+      // sign-extending add and the address shift per ray and step; every row
+      // word is read before the first mark, as below
+      constexpr int KM = CT::KM;
+      const uint32_t* p0 = ray_p0_words(L);
+      const uint32_t meta = C.rp[CT::RPW - 1];
+      Ray q[RPL];
+      uint32_t P0[RPL];
+#pragma unroll
+      for (int j = 0; j < RPL; ++j) {
+        const uint32_t mb = (meta >> (8 * j)) & 0xFFu;
+        q[j].K = (int)(mb & 31u) - 1;
+        q[j].live = (mb & 31u) != 0;
+        q[j].bits = q[j].d0 = q[j].d1 = 0;
+        P0[j] = p0[mb >> 5];
+      }
+      uint32_t Pk[KM][RPL];
+      WT nr[KM][RPL];
+#pragma unroll
+      for (int u = 0; u < KM; ++u) {
+#pragma unroll
+        for (int j = 0; j < RPL; ++j) {
+          const int i = j * KM + u;
+          const uint32_t w = C.rp[i >> 1];
+          const int32_t off = (i & 1) ? ((int32_t)w >> 16) : (int32_t)(int16_t)(w & 0xFFFFu);
+          Pk[u][j] = P0[j] + (uint32_t)off;
+          nr[u][j] = *lds_ptr<const WT>(Pk[u][j] >> 6);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < KM; ++u) {
+#pragma unroll
+        for (int j = 0; j < RPL; ++j) {
+          q[j].P = Pk[u][j];
+          ray_mark(C, q[j], u + 1, nr[u][j], (WT)0, sink_m, false, false, k1 != 0 && u == 0);
+        }
+      }
+      return;
+    }
     const int total = N * s.nbeams;
     // lane l of a pass takes rays RPL*l .. RPL*l+RPL-1: within one ds_or the
     // lanes of an agent hold beams RPL apart, which mostly land in different
@@ -1640,8 +1730,12 @@ __device__ __forceinline__ void set_agent(const State& s, const Lds<WT>& L, int 
 }
 
 template <class CT, typename WT = typename CT::WT>
-__device__ __forceinline__ void reset_env(const State& s, const CT& C, const int32_t* inj_pos) {
+__device__ __forceinline__ void reset_env(const State& s, const CT& C0, const int32_t* inj_pos) {
   constexpr int LPE = CT::LPE, KI = CT::KI;
+  // RAYPROG: the lane's program row again, for the initial sense (lands
+  // during the zeroing below) -- the step's copy then dies with its march
+  // instead of staying in registers up to here
+  const auto& C = with_ray_prog(s, C0);
   const Lds<WT>& L = C.L;
   const int N = s.N;
   const int e = C.e;
@@ -1679,6 +1773,8 @@ __device__ __forceinline__ void reset_env(const State& s, const CT& C, const int
         bad |= (inj_pos[((size_t)e * N + j) * 2] == x && inj_pos[((size_t)e * N + j) * 2 + 1] == y);
       if (bad) atomicOr(s.err, ERR_INJECT);
       set_agent<WT>(s, L, C.sub, x, y);
+      if constexpr (CT::RAYPROG)
+        ray_p0_words(L)[C.sub] = ray_p0(s, L, C.sub, x, y, (x - s.H - 1) >> 3, (y - s.H - 1) >> 3);
     }
   } else if (C.sub < 64) {
     // x = randint(W), y = randint(L); accept iff grid >= 0 and unoccupied;
@@ -1705,7 +1801,11 @@ __device__ __forceinline__ void reset_env(const State& s, const CT& C, const int
       }
     }
     if (placed < N && lane == 0) atomicOr(s.err, ERR_PLACEMENT);
-    if (lane < N) set_agent<WT>(s, L, lane, px, py);
+    if (lane < N) {
+      set_agent<WT>(s, L, lane, px, py);
+      if constexpr (CT::RAYPROG)
+        ray_p0_words(L)[lane] = ray_p0(s, L, lane, px, py, (px - s.H - 1) >> 3, (py - s.H - 1) >> 3);
+    }
   }
   // the zeroing stores must land before the window stores / atomics below
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2014,8 +2114,11 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
   const double dthresh0 = rl0.done_thresh;
   const bool lidar = s.sensor == 0;
   const int nbl = lidar ? s.nbeams : 1;  // a square env reads a dummy record
-  const int4 bm0 = reinterpret_cast<const int4*>(lidar ? (const void*)s.beams : (const void*)s.pos)
-      [C.sub < nbl ? C.sub : 0];
+  // (RAYPROG: the lane's ray program row instead of a beam record)
+  if constexpr (CT::RAYPROG) load_ray_prog(s, C);
+  const int4 bm0 = CT::RAYPROG ? make_int4(0, 0, 0, 0)
+                               : reinterpret_cast<const int4*>(lidar ? (const void*)s.beams : (const void*)s.pos)
+                                     [C.sub < nbl ? C.sub : 0];
   // fan march: the fan data (LUTs, sector and special records) instead of the
   // beam records, up to 3 * LPE int4 in this round trip
   const bool fan = fan_on(s);
@@ -2041,6 +2144,10 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
   // the branch that uses it (that would make it a round trip of its own)
   asm volatile("" ::"v"(p0.x), "v"(p0.y), "v"(act_raw), "v"(act0_raw), "v"(req_raw), "v"(g0),
                "v"(bm0.x), "v"(bm0.w), "v"(mwv.x), "v"(mwv.y), "v"(chd.x), "v"(chd.w), "v"(chb.y));
+  if constexpr (CT::RAYPROG) {
+#pragma unroll
+    for (int q = 0; q < CT::RPW; q += 4) asm volatile("" ::"v"(C.rp[q]));
+  }
   const int act = is_step ? act_raw : 255;
   // one env per workgroup: the env's flags are uniform -- made scalar
   // (readfirstlane), their branches are scalar branches instead of lane masks
@@ -2085,7 +2192,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
     if (C.sub + LPE < n16) dst[C.sub + LPE] = fv1;
     if (C.sub + 2 * LPE < n16) dst[C.sub + 2 * LPE] = fv2;
     for (int j = C.sub + 3 * LPE; j < n16; j += LPE) dst[j] = fsrc[j];
-  } else if (lidar) {
+  } else if (lidar && !CT::RAYPROG) {  // (RAYPROG: no beam records; their words hold the agents' P0)
     if (C.sub < s.nbeams) reinterpret_cast<int4*>(L.beams)[C.sub] = bm0;
     for (int b = C.sub + LPE; b < s.nbeams; b += LPE) L.beams[b] = s.beams[b];
   }
@@ -2459,16 +2566,20 @@ EnvLaunch select_env(const State& s, int nt, int epw) {
   const uint64_t mtb = (uint64_t)s.MT * 8;
   const bool fits32 = (uint64_t)s.B * s.N * mtb < (1ull << 32) && (uint64_t)s.G * mtb < (1ull << 32);
   const bool spec = getenv_spec();
+  // the compiled sparse-beam shapes of one wave march from the ray programs
+  // (Ctx::RAYPROG): without one (beam patterns that depend on the start, or
+  // MARLCOV_BEAM_TABLE) the generic kernel of the same geometry runs
+  const bool rp = s.ray_prog != nullptr;
   if (epw == 2) {
-    if (narrow && fits32 && spec && ShapeC2B::matches(s)) return MC_EL(64, 2, uint32_t, ShapeC2B, "u32,C2");
-    if (narrow && fits32 && spec && ShapeC2::matches(s)) return MC_EL(64, 2, uint32_t, ShapeC2, "u32,C2");
-    if (narrow && fits32 && spec && ShapeC2D::matches(s)) return MC_EL(64, 2, uint32_t, ShapeC2D, "u32,C2D");
+    if (narrow && fits32 && spec && rp && ShapeC2B::matches(s)) return MC_EL(64, 2, uint32_t, ShapeC2B, "u32,C2");
+    if (narrow && fits32 && spec && rp && ShapeC2::matches(s)) return MC_EL(64, 2, uint32_t, ShapeC2, "u32,C2");
+    if (narrow && fits32 && spec && rp && ShapeC2D::matches(s)) return MC_EL(64, 2, uint32_t, ShapeC2D, "u32,C2D");
     if (narrow) return MC_EL(64, 2, uint32_t, Dynamic, "u32,generic");
     return MC_EL(64, 2, uint64_t, Dynamic, "u64,generic");
   }
   if (narrow) {
-    if (nt == 64 && fits32 && spec && ShapeC2::matches(s)) return MC_EL(64, 1, uint32_t, ShapeC2, "u32,C2");
-    if (nt == 64 && fits32 && spec && ShapeC2D::matches(s)) return MC_EL(64, 1, uint32_t, ShapeC2D, "u32,C2D");
+    if (nt == 64 && fits32 && spec && rp && ShapeC2::matches(s)) return MC_EL(64, 1, uint32_t, ShapeC2, "u32,C2");
+    if (nt == 64 && fits32 && spec && rp && ShapeC2D::matches(s)) return MC_EL(64, 1, uint32_t, ShapeC2D, "u32,C2D");
     if (nt == 128 && spec && ShapeC5B::matches(s)) return MC_EL(128, 1, uint32_t, ShapeC5B, "u32,C5");
     if (nt == 128 && spec && ShapeC5::matches(s)) return MC_EL(128, 1, uint32_t, ShapeC5, "u32,C5");
     return generic_env<uint32_t>(nt);
