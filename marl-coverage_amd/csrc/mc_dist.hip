@@ -113,29 +113,37 @@ __device__ __forceinline__ u16x2 dpp2(u16x2 v) {  // source lane out of the row:
   return __builtin_bit_cast(u16x2, __builtin_amdgcn_update_dpp((int)0xFFFFFFFF, __builtin_bit_cast(int, v),
                                                                CTRL, 0xF, 0xF, false));
 }
-// 64 chunks (1024 threads): the whole wave, four 16-lane rows
-__device__ __forceinline__ u16x2 excl_prefix_min64(u16x2 v) {
-  const int l = opaque_tid() & 63;
+// inclusive minima within each 16-lane row: from the row's first lane up to
+// this one (row_shr 1, 2, 4, 8) / from this lane to the row's last (row_shl)
+__device__ __forceinline__ u16x2 row_incl_min_shr(u16x2 v) {
   u16x2 x = __builtin_elementwise_min(v, dpp2<0x111>(v));
   x = __builtin_elementwise_min(x, dpp2<0x112>(x));
   x = __builtin_elementwise_min(x, dpp2<0x114>(x));
-  x = __builtin_elementwise_min(x, dpp2<0x118>(x));  // inclusive within the row
+  return __builtin_elementwise_min(x, dpp2<0x118>(x));
+}
+__device__ __forceinline__ u16x2 row_incl_min_shl(u16x2 v) {
+  u16x2 x = __builtin_elementwise_min(v, dpp2<0x101>(v));
+  x = __builtin_elementwise_min(x, dpp2<0x102>(x));
+  x = __builtin_elementwise_min(x, dpp2<0x104>(x));
+  return __builtin_elementwise_min(x, dpp2<0x108>(x));
+}
+// 64 chunks (1024 threads): the whole wave, four 16-lane rows
+__device__ __forceinline__ u16x2 excl_prefix_min64(u16x2 v) {
+  const int l = opaque_tid() & 63;
+  const u16x2 x = row_incl_min_shr(v);
   const u16x2 t0 = __builtin_bit_cast(u16x2, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 15));
   const u16x2 t1 = __builtin_bit_cast(u16x2, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 31));
   const u16x2 t2 = __builtin_bit_cast(u16x2, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 47));
   const u16x2 c1 = t0, c2 = __builtin_elementwise_min(t0, t1), c3 = __builtin_elementwise_min(c2, t2);
   const int row = l >> 4;
   const u16x2 carry = row == 0 ? kNone2 : (row == 1 ? c1 : (row == 2 ? c2 : c3));  // the rows before
-  u16x2 e = dpp2<0x111>(x);
+  u16x2 e = dpp2<0x111>(x);  // exclusive within the row
   e = (l & 15) == 0 ? kNone2 : e;
   return __builtin_elementwise_min(e, carry);
 }
 __device__ __forceinline__ u16x2 excl_suffix_min64(u16x2 v) {
   const int l = opaque_tid() & 63;
-  u16x2 x = __builtin_elementwise_min(v, dpp2<0x101>(v));
-  x = __builtin_elementwise_min(x, dpp2<0x102>(x));
-  x = __builtin_elementwise_min(x, dpp2<0x104>(x));
-  x = __builtin_elementwise_min(x, dpp2<0x108>(x));  // inclusive within the row, from the right
+  const u16x2 x = row_incl_min_shl(v);
   const u16x2 s1 = __builtin_bit_cast(u16x2, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 16));
   const u16x2 s2 = __builtin_bit_cast(u16x2, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 32));
   const u16x2 s3 = __builtin_bit_cast(u16x2, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 48));
@@ -146,25 +154,20 @@ __device__ __forceinline__ u16x2 excl_suffix_min64(u16x2 v) {
   e = (l & 15) == 15 ? kNone2 : e;
   return __builtin_elementwise_min(e, carry);
 }
+// 32 chunks (512 threads): a half wave, two 16-lane rows
 __device__ __forceinline__ u16x2 excl_prefix_min32(u16x2 v) {
   const int l = opaque_tid() & 63;
-  u16x2 x = __builtin_elementwise_min(v, dpp2<0x111>(v));  // row_shr:1
-  x = __builtin_elementwise_min(x, dpp2<0x112>(x));        // row_shr:2
-  x = __builtin_elementwise_min(x, dpp2<0x114>(x));        // row_shr:4
-  x = __builtin_elementwise_min(x, dpp2<0x118>(x));        // row_shr:8: inclusive within the row
+  const u16x2 x = row_incl_min_shr(v);
   const u16x2 r0 = __builtin_bit_cast(u16x2, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 15));
   const u16x2 r2 = __builtin_bit_cast(u16x2, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 47));
   const u16x2 carry = (l & 16) ? ((l & 32) ? r2 : r0) : kNone2;  // rows 1, 3: the row before
-  u16x2 e = dpp2<0x111>(x);                                     // exclusive within the row
+  u16x2 e = dpp2<0x111>(x);
   e = (l & 15) == 0 ? kNone2 : e;
   return __builtin_elementwise_min(e, carry);
 }
 __device__ __forceinline__ u16x2 excl_suffix_min32(u16x2 v) {
   const int l = opaque_tid() & 63;
-  u16x2 x = __builtin_elementwise_min(v, dpp2<0x101>(v));  // row_shl:1
-  x = __builtin_elementwise_min(x, dpp2<0x102>(x));        // row_shl:2
-  x = __builtin_elementwise_min(x, dpp2<0x104>(x));        // row_shl:4
-  x = __builtin_elementwise_min(x, dpp2<0x108>(x));        // row_shl:8
+  const u16x2 x = row_incl_min_shl(v);
   const u16x2 r1 = __builtin_bit_cast(u16x2, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 16));
   const u16x2 r3 = __builtin_bit_cast(u16x2, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 48));
   const u16x2 carry = (l & 16) ? kNone2 : ((l & 32) ? r3 : r1);  // rows 0, 2: the row after
@@ -233,14 +236,6 @@ __device__ __forceinline__ int2 ld_sc1(const int2* p) {
   const unsigned long long v = ld_sc1(reinterpret_cast<const unsigned long long*>(p));
   return make_int2((int)(uint32_t)v, (int)(uint32_t)(v >> 32));
 }
-// plain or `sc1`
-template <typename T>
-__device__ __forceinline__ T ld_ho(const T* p, bool sc1) { return sc1 ? ld_sc1(p) : *p; }
-template <typename T>
-__device__ __forceinline__ void st_ho(T* p, T v, bool sc1) {
-  if (sc1) st_sc1(p, v);
-  else *p = v;
-}
 
 // max over the wave (every lane gets it)
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
@@ -267,6 +262,205 @@ __device__ __forceinline__ uint32_t list_entry(const State& s, const ListView& v
   for (int k = 1; k < kListShards; ++k) off = i >= v.pre[k] ? (uint32_t)k * s.dist_cap + (i - v.pre[k]) : off;
   return list[off];
 }
+
+// ---- the pieces dist_kernel_t and dist_big_kernel share
+
+// target t -> extended cell (u, v): [0, 5) the end cells of the next step
+// (quirk: distance_map[x, y] with the padded-grid (x, y), no pad offset),
+// [5, 5 + E*E) the crop (POST only)
+__device__ __forceinline__ void target_ext(int t, int px, int py, int pad, int ego, int E, int& u, int& v) {
+  if (t >= 5) {
+    const int r = (t - 5) / E, c = (t - 5) - r * E;
+    u = px + pad - ego + r;
+    v = py + pad - ego + c;
+  } else {
+    u = px + (t == 1 ? 1 : (t == 3 ? -1 : 0));
+    v = py + (t == 2 ? 1 : (t == 4 ? -1 : 0));
+  }
+}
+
+// The 8 tiles of map word w in tile row ti (columns 64 w .. 64 w + 63 of 8
+// map rows) as dwords: lo[j] = rows 0-3 of tile j, hi[j] = rows 4-7.  Tiles
+// (ti, tj), (ti, tj + 1) of an even tj are adjacent in the block layout: one
+// 16-byte load per pair (the block's padding columns exist; a tile past the
+// last tile column, and every tile when !ok, reads as 0)
+__device__ __forceinline__ void load_tile_row8(const State& s, const uint64_t* free_t, int ti, int w, bool ok,
+                                               uint32_t (&lo)[8], uint32_t (&hi)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; j += 2) {
+    const int tj = 8 * w + j;
+    uint4 t = make_uint4(0u, 0u, 0u, 0u);
+    if (ok && tj < s.TC) t = *reinterpret_cast<const uint4*>(free_t + tile_index(s.TCS, ti, tj));
+    if (tj + 1 >= s.TC) t.z = t.w = 0u;
+    lo[j] = t.x;
+    hi[j] = t.y;
+    lo[j + 1] = t.z;
+    hi[j + 1] = t.w;
+  }
+}
+// v_perm selector: byte r & 3 of two dwords -> bytes 0, 1 (bytes 2, 3 zero)
+__device__ __forceinline__ uint32_t row_byte_sel(int r) {
+  const uint32_t b = (uint32_t)(r & 3);
+  return b | ((4u + b) << 8) | 0x0C0C0000u;
+}
+// row r of those 8 tiles as one 64-column word (the byte transpose: byte j of
+// the word = byte r of tile j): tile pairs (j, j + 1) -> bytes 0, 1 of a
+// dword, then two such pairs -> 4 bytes
+__device__ __forceinline__ uint64_t tile_row_word(const uint32_t (&lo)[8], const uint32_t (&hi)[8], int r) {
+  const uint32_t* src = r < 4 ? lo : hi;
+  const uint32_t sel2 = row_byte_sel(r);
+  const uint32_t p01 = __builtin_amdgcn_perm(src[1], src[0], sel2);
+  const uint32_t p23 = __builtin_amdgcn_perm(src[3], src[2], sel2);
+  const uint32_t p45 = __builtin_amdgcn_perm(src[5], src[4], sel2);
+  const uint32_t p67 = __builtin_amdgcn_perm(src[7], src[6], sel2);
+  const uint32_t wlo = __builtin_amdgcn_perm(p23, p01, 0x05040100u);
+  const uint32_t whi = __builtin_amdgcn_perm(p67, p45, 0x05040100u);
+  return (uint64_t)wlo | ((uint64_t)whi << 32);
+}
+
+// a row with no covered cell anywhere (strip padding, the pad ring)
+__device__ __forceinline__ void row_pass_none(uint2* grow) {
+#pragma unroll
+  for (int k = 0; k < kStrip / 4; ++k) grow[k] = make_uint2(~0u, ~0u);
+}
+
+// Column pass of one strip in G ([CH * CL rows][SP u16]): column pair `pair`
+// (two columns as the low / high u16 halves of one packed register;
+// saturating u16 pairs, 0xFFFF = no covered cell) over the CL rows from u0c.
+// Leaves d of the chunk's cells in tp (0 in the padding rows, rowmask) and
+// the best (d << 16 | u) of either column in klo / khi; returns the row base
+// u0, made opaque per strip: the compiler would otherwise hoist CL
+// loop-invariant row values out of the strip loop (and spill them).  One
+// workgroup barrier between the G reads and the scans.
+template <int CL, int CH, int SP>
+__device__ __forceinline__ int column_pass(const uint16_t* G, int u0c, int pair, uint32_t rowmask, u16x2 (&tp)[CL],
+                                           uint32_t& klo, uint32_t& khi) {
+  int u0 = u0c;
+  asm volatile("" : "+v"(u0));
+  const uint32_t* g32 = reinterpret_cast<const uint32_t*>(G) + u0 * (SP / 2) + pair;
+  u16x2 sd[CL];  // tp: g + K - u (then d), sd: g + u (then the "down" distance)
+  u16x2 pm = kNone2, sm = kNone2;
+#pragma unroll
+  for (int i = 0; i < CL; ++i) {
+    const u16x2 g = __builtin_bit_cast(u16x2, g32[i * (SP / 2)]);
+    const u16x2 uu = splat2(u0 + i);
+    tp[i] = __builtin_elementwise_sub_sat(__builtin_elementwise_add_sat(g, kRowOff2), uu);
+    sd[i] = __builtin_elementwise_add_sat(g, uu);
+    pm = __builtin_elementwise_min(pm, tp[i]);
+    sm = __builtin_elementwise_min(sm, sd[i]);
+  }
+  __syncthreads();  // every G read of the strip is done: the next row pass may write
+  // minima over the pair's chunks before / after this one (its CH chunks are
+  // the lanes of a half wave or a wave)
+  u16x2 run, sfx;
+  if constexpr (CH == 64) {
+    run = excl_prefix_min64(pm);
+    sfx = excl_suffix_min64(sm);
+  } else {
+    run = excl_prefix_min32(pm);
+    sfx = excl_suffix_min32(sm);
+  }
+  // suffix scan: the "down" distance min_{u'>=u} g(u') + u' - u
+#pragma unroll
+  for (int i = CL - 1; i >= 0; --i) {
+    sfx = __builtin_elementwise_min(sfx, sd[i]);
+    sd[i] = __builtin_elementwise_sub_sat(sfx, splat2(u0 + i));
+  }
+  // prefix scan, d = min(up, down), the best (d << 16 | u) of each column
+  // over the chunk's grid rows (the last chunk's padding rows count 0)
+  klo = khi = 0;
+#pragma unroll
+  for (int i = 0; i < CL; ++i) {
+    const u16x2 uu = splat2(u0 + i);
+    run = __builtin_elementwise_min(run, tp[i]);
+    const u16x2 up = __builtin_elementwise_sub_sat(__builtin_elementwise_add_sat(run, uu), kRowOff2);
+    const uint32_t d = __builtin_bit_cast(uint32_t, __builtin_elementwise_min(up, sd[i])) &
+                       (uint32_t)__builtin_amdgcn_sbfe((int)rowmask, i, 1);
+    tp[i] = __builtin_bit_cast(u16x2, d);
+    klo = max(klo, (d << 16) | (uint32_t)(u0 + i));
+    khi = max(khi, (d & 0xFFFF0000u) | (uint32_t)(u0 + i));
+  }
+  return u0;
+}
+
+// the thread's best (d << 16 | u) and its column, over columns v, v + 1 < RY
+// (ties: the largest u)
+__device__ __forceinline__ void best_update(uint32_t klo, uint32_t khi, int v, int RY, uint32_t& bestkey, int& bestv) {
+  if (v < RY && klo > bestkey) {
+    bestkey = klo;
+    bestv = v;
+  }
+  if (v + 1 < RY && khi > bestkey) {
+    bestkey = khi;
+    bestv = v + 1;
+  }
+}
+
+// The thread's best cell into the map's key: max over the map of (d, distance
+// from the robot, u, v).  Witness: of the maxima, the one farthest from the
+// robot (new coverage comes from around the robot, so it keeps M valid
+// longest).  16 bits per field: d, far, u, v are all < 65535 (mc_create
+// bounds width + length + 4 pad), so wide grids keep an exact witness
+__device__ __forceinline__ void publish_key(unsigned long long* key, uint32_t bestkey, int bestv, int px, int py,
+                                            int pad) {
+  const int vmax = (int)(bestkey >> 16);
+  const int ubest = (int)(bestkey & 0xFFFF), vbest = bestv;
+  const int far = abs(ubest - (px + pad)) + abs(vbest - (py + pad));
+  atomicMax(key, ((unsigned long long)vmax << 48) | ((unsigned long long)far << 32) |
+                     ((unsigned long long)ubest << 16) | (unsigned long long)vbest);
+}
+
+// A transformed map's outputs: (M, witness) from the map's key (one thread;
+// M unknown (-1) while nothing is covered: every step recomputes it)
+__device__ __forceinline__ void write_map_mw(const State& s, uint32_t ea, int pad, int M, unsigned long long key) {
+  const int wu = (int)((key >> 16) & 0xFFFF), wv = (int)(key & 0xFFFF);
+  reinterpret_cast<int2*>(s.dist_mw)[ea] = make_int2(M, pack_witness(wu - pad, wv - pad));
+}
+// and its PRE data and (POST) obs crop from the targets' d (NTH threads).  No covered cell: the restatement's convention (-1 everywhere);
+// only the discarded reset-time PRE term can see it
+template <int NTH>
+__device__ __forceinline__ void write_map_terms(int tid, uint32_t ea, int post, int T, int E, bool cov, float Mf,
+                                                const int* s_d, float* pre_out, float* dist_obs) {
+  if (post) {
+    float* dst = dist_obs + (size_t)ea * E * E;
+    for (int t = 5 + tid; t < T; t += NTH) dst[t - 5] = dist_value((float)(cov ? s_d[t] : -1), Mf);
+  }
+  float* pd = pre_out + (size_t)ea * 8;
+  if (tid == 0) pd[0] = Mf;
+  if (tid < 5) pd[1 + tid] = (float)(cov ? s_d[tid] : -1);
+}
+
+// The work list's bookkeeping at the end of a listed launch (one thread per
+// workgroup).  The shards' counts (State::dist_shc) = entries, count[1] =
+// workgroups done: the last workgroup to finish zeroes them for the next
+// step's env kernel (every workgroup has read the entry count before it
+// counts itself done; no memset launch per step) and keeps the entry count in
+// count[2] (MC_FIELD_DIST_LISTED); the cache hits count[3] go to count[4] the
+// same way (MC_FIELD_DIST_CACHED)
+__device__ __forceinline__ void list_done(const State& s, uint32_t* cnt, uint32_t n_items) {
+  if (n_items == 0) {
+    if (blockIdx.x == 0) {
+      cnt[2] = cnt[4] = 0;
+      if (s.dist_tot) s.dist_tot[3] += 1ull;
+    }
+  } else {
+    __threadfence();
+    if (atomicAdd(cnt + 1, 1u) == gridDim.x - 1) {
+      uint32_t nl = 0;
+      for (int k = 0; k < kListShards; ++k) nl += atomicExch(s.dist_shc + k * kShardStride, 0u);
+      const uint32_t nh = atomicExch(cnt + 3, 0u);
+      atomicExch(cnt + 2, nl);
+      atomicExch(cnt + 4, nh);
+      atomicExch(cnt + 1, 0u);
+      if (s.dist_tot) {  // MC_FIELD_DIST_TOTALS: the cache hits were served
+        s.dist_tot[0] += nl;
+        s.dist_tot[1] += nh;
+        s.dist_tot[2] += nl - nh;
+        s.dist_tot[3] += 1ull;
+      }
+    }
+  }
+}
 }  // namespace
 
 // rows per column chunk: the instantiation (8, 17 or 26) whose kCh chunks
@@ -277,9 +471,9 @@ __host__ __device__ constexpr int chunk_rows(int RX) {
 }
 
 // LDS carve of the full transform (bytes): row bitboard | strip (u16, also the
-// tile staging area) | chunk minima | targets
+// tile staging area) | targets
 struct DtLds {
-  size_t cb, strip, mins, tgt, total;
+  size_t cb, strip, tgt, total;
 };
 __host__ __device__ inline DtLds dt_lds(int RX, int RY, int MT, int T) {
   DtLds L;
@@ -289,9 +483,8 @@ __host__ __device__ inline DtLds dt_lds(int RX, int RY, int MT, int T) {
   // (at most RX x RW words)
   const size_t st = (size_t)kCh * chunk_rows(RX) * kSP * 2, tiles = (size_t)RX * RW * 8;
   L.strip = ((st > tiles ? st : tiles) + 15) & ~(size_t)15;
-  L.mins = 0;
   L.tgt = ((size_t)T * 4 + 15) & ~(size_t)15;
-  L.total = L.cb + L.strip + L.mins + L.tgt;
+  L.total = L.cb + L.strip + L.tgt;
   return L;
 }
 
@@ -540,16 +733,12 @@ __device__ __forceinline__ void cache_serve(const State& s, int T, uint32_t ea, 
 //      S from the list length: the few full transforms of a steady state
 //      step are latency-bound in one workgroup): a part transforms its
 //      strips and publishes its best key, strip maxima, target cells and
-//      cache candidates (State::dist_g*); with S == 1 the one part
-//      finalises the map as mode 0 does
-//   3  (no longer launched: since round 5 the part that arrives last at the
-//      map's counter, State::dist_pcnt, merges inside mode 2, the hand-off
-//      above; the kernel's mode-3 branches are still there)
-//      the full list after mode 2 (S > 1): one workgroup per map merges the
-//      parts' partials and finalises the map (the bitboard is staged only
-//      for a second cache pass).  A launch boundary orders the parts'
-//      stores before the merge: no per-map done counter, no device-scope
-//      fences between the XCDs' L2s
+//      cache candidates (State::dist_g*), then counts itself at the map's
+//      counter (State::dist_pcnt); the part that arrives last merges the
+//      parts' partials (merge_parts, the hand-off above) and finalises the
+//      map; with S == 1 the one part finalises the map as mode 0 does
+// (A mode 3, a second launch that merged the parts, went in round 10; its
+// number is not reused.)
 constexpr int kSplitSlots = 512;  // workgroups resident at once (2 per CU)
 #ifndef MC_MAX_PARTS  // build knob (A/B): parts per split map
 #define MC_MAX_PARTS 8
@@ -644,7 +833,7 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
   uint64_t* Cb = reinterpret_cast<uint64_t*>(smem);
   uint16_t* G = reinterpret_cast<uint16_t*>(smem + LL.cb);  // [kCh * kCL][kSP] (kStrip used)
   constexpr int RXP = kCh * kCL;                             // strip rows incl. padding
-  int* s_d = reinterpret_cast<int*>(smem + LL.cb + LL.strip + LL.mins);
+  int* s_d = reinterpret_cast<int*>(smem + LL.cb + LL.strip);
   const uint64_t last = (RY & 63) ? low_mask(RY & 63) : ~0ull;
   // every map (list == nullptr: one workgroup per (env, agent)), or the maps
   // of a device work list (a fixed grid strides over *count entries: the
@@ -652,15 +841,13 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
   const int nstrips_all = (RY + kStrip - 1) / kStrip;
   uint64_t tk = 0;  // (diagnostic) the workgroup's start
   DSTAMP(tk);
-  const uint32_t nF = mode >= 2 ? __atomic_load_n(full, __ATOMIC_RELAXED) : 0u;
-  const int S = mode >= 2 && nF > 0 ? max(1, min(min(nstrips_all, kMaxParts), (int)(kSplitSlots / nF))) : 1;
+  const uint32_t nF = mode == 2 ? __atomic_load_n(full, __ATOMIC_RELAXED) : 0u;
+  const int S = mode == 2 && nF > 0 ? max(1, min(min(nstrips_all, kMaxParts), (int)(kSplitSlots / nF))) : 1;
   ListView lv;
   lv.pre[kListShards] = 0;
   if (list && mode < 2) lv = list_view(s);
-  const uint32_t n_items = mode == 2   ? nF * (uint32_t)S
-                           : mode == 3 ? (S > 1 ? nF : 0u)
-                                       : (list ? lv.pre[kListShards] : (uint32_t)gridDim.x);
-  const bool strided = mode >= 2 || list != nullptr;
+  const uint32_t n_items = mode == 2 ? nF * (uint32_t)S : (list ? lv.pre[kListShards] : (uint32_t)gridDim.x);
+  const bool strided = mode == 2 || list != nullptr;
   if (mode == 2 && blockIdx.x == 0 && tid == 0) {
     // mode 1 has drained the list: its counters for the diagnostics
     // (MC_FIELD_DIST_LISTED / _CACHED: every listed map was either served by
@@ -690,16 +877,15 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
     // lane, ~24 MB of scratch writes per C5 step) at <17>, none with this
     const int tid = opaque_tid();
     dist_reload(s, io);
-    // modes 2 / 3: the full-list entry (and mode 2's part)
-    const uint32_t fi = mode == 2 ? it / (uint32_t)S : (mode == 3 ? it : 0u);
+    // mode 2: the full-list entry and the part
+    const uint32_t fi = mode == 2 ? it / (uint32_t)S : 0u;
     const int part = mode == 2 ? (int)(it - fi * (uint32_t)S) : 0;
     if (fi >= nF && mode == 2) continue;
-    const uint32_t ea = mode >= 2 ? full[8 + 2 * fi] : (list ? list_entry(s, lv, list, it) : it);
+    const uint32_t ea = mode == 2 ? full[8 + 2 * fi] : (list ? list_entry(s, lv, list, it) : it);
     // the strips this workgroup transforms: a contiguous range, the ranges
     // splitting the map's running strips evenly (strip_run_mask; without a
     // mask, its strips)
     int st_lo = part * nstrips_all / S, st_hi = (part + 1) * nstrips_all / S;
-    bool idle = false;  // (never set: the idle-part skip is gone; the flag leaves with the mode-3 branches)
     if (mode == 2 && S > 1 && s.dist_rmask) {
       const uint64_t rm = s.dist_rmask[ea];
       if (rm) {
@@ -722,20 +908,6 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
     const uint64_t* free_t = s.freem + (size_t)ea * s.MT;
     const int2 pp = reinterpret_cast<const int2*>(s.pos)[ea];
     const int px = pp.x, py = pp.y;
-
-    // target t -> extended cell (u, v): [0, 5) the end cells of the next step
-    // (quirk: distance_map[x, y] with the padded-grid (x, y), no pad offset),
-    // [5, 5 + E*E) the crop (POST only)
-    auto target = [&](int t, int& u, int& v) {
-      if (t >= 5) {
-        const int r = (t - 5) / E, c = (t - 5) - r * E;
-        u = px + pad - s.ego + r;
-        v = py + pad - s.ego + c;
-      } else {
-        u = px + (t == 1 ? 1 : (t == 3 ? -1 : 0));
-        v = py + (t == 2 ? 1 : (t == 4 ? -1 : 0));
-      }
-    };
     for (int t = tid; t < T; t += kDtThreads) s_d[t] = -1;
     if (tid == 0) {
       s_key = 0;
@@ -780,13 +952,12 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
     // the exact current d of the cached cells (the fast path computed them
     // before it failed): a lower bound of the new max(d)
     // (a try that returned before staging -- box too large -- leaves none)
-    const int theta0 = mode >= 2 ? (int)full[9 + 2 * fi] : (tried ? (int)(s_fkey >> 16) : 0);
-    bool need_cb = true;  // the map's bitboard in LDS
+    const int theta0 = mode == 2 ? (int)full[9 + 2 * fi] : (tried ? (int)(s_fkey >> 16) : 0);
     // ---- merge a split map's parts' partials: the best key, the raw target
     // d (in the output buffers), the strip maxima, the cache candidates.
-    // Mode 3 (a launch after mode 2: plain loads), or the part of a fused
-    // mode 2 that finished last (`sc1` loads of the parts' `sc1` stores)
-    auto merge_parts = [&](bool sc1) {
+    // Run by the part of a split map that finished last: `sc1` loads of the
+    // parts' `sc1` stores
+    auto merge_parts = [&]() {
       __syncthreads();  // the item's LDS scalars are initialised; every thread is past its own list
       if (tid == 0) s_ccount = 0;
       __syncthreads();
@@ -798,18 +969,18 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
       bool over = false;
 #pragma unroll
       for (int p = 0; p < kMaxParts; ++p) {
-        const uint32_t c = (lists && p < S) ? ld_ho(s.dist_gcnt + (size_t)fi * kDistGParts + p, sc1) : 0u;
+        const uint32_t c = (lists && p < S) ? ld_sc1(s.dist_gcnt + (size_t)fi * kDistGParts + p) : 0u;
         over |= c > (uint32_t)kDistK;
         pre[p + 1] = pre[p] + (c > (uint32_t)kDistK ? 0u : c);
       }
       const uint32_t total = pre[kMaxParts];
-      const unsigned long long gk = ld_ho(s.dist_gkey + ea, sc1);
+      const unsigned long long gk = ld_sc1(s.dist_gkey + ea);
       const int thr = (int)(gk >> 48) - kDistT;  // the candidates that are cache cells
       for (int t = tid; t < T; t += kDtThreads)
-        s_d[t] = (int)(t < 5 ? ld_ho(pre_out + (size_t)ea * 8 + 1 + t, sc1)
-                             : ld_ho(dist_obs + (size_t)ea * E * E + (t - 5), sc1));
+        s_d[t] = (int)(t < 5 ? ld_sc1(pre_out + (size_t)ea * 8 + 1 + t)
+                             : ld_sc1(dist_obs + (size_t)ea * E * E + (t - 5)));
       for (int st = tid; st < min(nstrips_all, kMaxTrack); st += kDtThreads)
-        s_smax[st] = (int)ld_ho(s.dist_sm + (size_t)ea * kMaxTrack + st, sc1);
+        s_smax[st] = (int)ld_sc1(s.dist_sm + (size_t)ea * kMaxTrack + st);
       if (gk != 0 && !over)
         for (int k = tid; k < (int)total; k += kDtThreads) {
           // segment p holds candidates pre[p] .. pre[p + 1] - 1
@@ -822,7 +993,7 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
               base = pre[q];
             }
           const size_t at = ((size_t)fi * kDistGParts + p) * kDistK + ((uint32_t)k - base);
-          const int2 c = ld_ho(s.dist_gcand + at, sc1);
+          const int2 c = ld_sc1(s.dist_gcand + at);
           if (c.y >= thr) {
             const int j = atomicAdd(&s_ccount, 1);
             if (j < kDistK) {
@@ -841,10 +1012,6 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
       if (tid < S) s.dist_gcnt[(size_t)fi * kDistGParts + tid] = 0;
       __syncthreads();
     };
-    if (mode == 3) {
-      merge_parts(false);
-      need_cb = s_cov && !(theta0 > 0 && s_ccount <= kDistK);  // the second pass
-    }
     // the map's row bitboard (Cb) in LDS
     auto stage_cb = [&]() {
       if (pad <= 16) {
@@ -866,17 +1033,7 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
           for (int k = 0; k < 2; ++k) {
             const int q = q0 + k * kDtThreads;
             const int ti = q / RW, w = q - ti * RW;
-#pragma unroll
-            for (int j = 0; j < 8; j += 2) {
-              const int tj = 8 * w + j;
-              uint4 t = make_uint4(0u, 0u, 0u, 0u);
-              if (q < nq && tj < s.TC) t = *reinterpret_cast<const uint4*>(free_t + tile_index(s.TCS, ti, tj));
-              if (tj + 1 >= s.TC) t.z = t.w = 0u;
-              lo[k][j] = t.x;
-              hi[k][j] = t.y;
-              lo[k][j + 1] = t.z;
-              hi[k][j + 1] = t.w;
-            }
+            load_tile_row8(s, free_t, ti, w, q < nq, lo[k], hi[k]);
             const int tp = 8 * w - 2;  // even: one 16-byte load (both tiles < TC when w <= RWm)
             uint4 t = make_uint4(0u, 0u, 0u, 0u);
             if (q < nq && pad > 0 && w > 0 && tp < s.TC) t = *reinterpret_cast<const uint4*>(free_t + tile_index(s.TCS, ti, tp));
@@ -896,21 +1053,10 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
               if (r >= nr) break;
-              const uint32_t* src = r < 4 ? lo[k] : hi[k];
-              const uint32_t* psrc = r < 4 ? plo[k] : phi[k];
-              const uint32_t b = (uint32_t)(r & 3);
-              // byte b of src[j]: pairs (j, j + 1) -> bytes 0, 1 of a dword,
-              // then two such pairs -> 4 bytes
-              const uint32_t sel2 = b | ((4u + b) << 8) | 0x0C0C0000u;
-              const uint32_t p01 = __builtin_amdgcn_perm(src[1], src[0], sel2);
-              const uint32_t p23 = __builtin_amdgcn_perm(src[3], src[2], sel2);
-              const uint32_t p45 = __builtin_amdgcn_perm(src[5], src[4], sel2);
-              const uint32_t p67 = __builtin_amdgcn_perm(src[7], src[6], sel2);
-              const uint32_t wlo = __builtin_amdgcn_perm(p23, p01, 0x05040100u);
-              const uint32_t whi = __builtin_amdgcn_perm(p67, p45, 0x05040100u);
-              const uint64_t cur = (uint64_t)wlo | ((uint64_t)whi << 32);
+              const uint64_t cur = tile_row_word(lo[k], hi[k], r);
               // bits 48..63 of map word w - 1 (tiles 8w-2, 8w-1) as 16 bits
-              const uint32_t prev16 = __builtin_amdgcn_perm(psrc[1], psrc[0], sel2);
+              const uint32_t* psrc = r < 4 ? plo[k] : phi[k];
+              const uint32_t prev16 = __builtin_amdgcn_perm(psrc[1], psrc[0], row_byte_sel(r));
               const uint64_t c = (pad > 0 ? ((cur << pad) | (uint64_t)(prev16 >> (16 - pad))) : cur) & wm;
               Cb[(size_t)(pad + 8 * ti + r) * RW + w] = c;
               any |= c != 0ull;
@@ -946,20 +1092,7 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
           for (int k = 0; k < 2; ++k) {
             const int q = q0 + k * kDtThreads;
             const int ti = q / RWm, w = q - ti * RWm;
-            // tiles (ti, tj), (ti, tj + 1) of an even tj are adjacent in the
-            // block layout: one 16-byte load per pair (the block's padding
-            // columns exist; a tile past the last column reads as 0)
-#pragma unroll
-            for (int j = 0; j < 8; j += 2) {
-              const int tj = 8 * w + j;
-              uint4 t = make_uint4(0u, 0u, 0u, 0u);
-              if (q < nq && tj < s.TC) t = *reinterpret_cast<const uint4*>(free_t + tile_index(s.TCS, ti, tj));
-              if (tj + 1 >= s.TC) t.z = t.w = 0u;
-              lo[k][j] = t.x;
-              hi[k][j] = t.y;
-              lo[k][j + 1] = t.z;
-              hi[k][j + 1] = t.w;
-            }
+            load_tile_row8(s, free_t, ti, w, q < nq, lo[k], hi[k]);
           }
 #pragma unroll
           for (int k = 0; k < 2; ++k) {
@@ -970,18 +1103,7 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
               if (r >= nr) break;
-              const uint32_t* src = r < 4 ? lo[k] : hi[k];
-              const uint32_t b = (uint32_t)(r & 3);
-              // byte b of src[j]: pairs (j, j + 1) -> bytes 0, 1 of a dword,
-              // then two such pairs -> 4 bytes
-              const uint32_t sel2 = b | ((4u + b) << 8) | 0x0C0C0000u;
-              const uint32_t p01 = __builtin_amdgcn_perm(src[1], src[0], sel2);
-              const uint32_t p23 = __builtin_amdgcn_perm(src[3], src[2], sel2);
-              const uint32_t p45 = __builtin_amdgcn_perm(src[5], src[4], sel2);
-              const uint32_t p67 = __builtin_amdgcn_perm(src[7], src[6], sel2);
-              const uint32_t wlo = __builtin_amdgcn_perm(p23, p01, 0x05040100u);
-              const uint32_t whi = __builtin_amdgcn_perm(p67, p45, 0x05040100u);
-              crw[(size_t)(8 * ti + r) * RWm + w] = (uint64_t)wlo | ((uint64_t)whi << 32);
+              crw[(size_t)(8 * ti + r) * RWm + w] = tile_row_word(lo[k], hi[k], r);
             }
           }
         }
@@ -1017,9 +1139,8 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
       }
       __syncthreads();
     };
-    if (!fast && need_cb && !idle) {
-      if (mode != 3)  // (mode 3 holds the parts' targets)
-        for (int t = tid; t < T; t += kDtThreads) s_d[t] = -1;
+    if (!fast) {
+      for (int t = tid; t < T; t += kDtThreads) s_d[t] = -1;
       stage_cb();
     }
     bool cov = fast || s_cov != 0;
@@ -1047,14 +1168,16 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
     auto strip = [&](int st, int thr, int cthr) {
       const int c0 = st * kStrip, w = c0 >> 6, h = (c0 >> 5) & 1;
       // ---- row pass: g of the strip's 32 cells of row u, as 16 u16 pairs
+      // (the g computation from `lc` on is repeated in dist_big_kernel: as a
+      // shared function it cost registers or spills in every spelling tried,
+      // profiles/r10/dist_shared/ -- change both)
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         const int u = tid + q * kDtThreads;
         if (u >= RXP) continue;
         uint2* grow = reinterpret_cast<uint2*>(G + u * kSP);
         if (u >= RX) {  // padding rows: no covered cell
-#pragma unroll
-          for (int k = 0; k < 8; ++k) grow[k] = make_uint2(~0u, ~0u);
+          row_pass_none(grow);
           continue;
         }
         const uint64_t cw = Cb[u * RW + w];
@@ -1118,56 +1241,10 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
         if (sb == ~0u) lastL[q] = c0 + 31;
       }
       __syncthreads();
-      // ---- column pass: column pair p (columns c0 + 2p, c0 + 2p + 1 as the
-      // low / high u16 halves of one packed register; saturating u16 pairs,
-      // 0xFFFF = no covered cell) over chunk c of kCL rows.  u0 is made opaque
-      // per strip: the compiler would otherwise hoist kCL loop-invariant row
-      // values out of the strip loop (and spill them)
-      int u0 = u0c;
-      asm volatile("" : "+v"(u0));
-      const uint32_t* g32 = reinterpret_cast<const uint32_t*>(G) + u0 * (kSP / 2) + pair;
-      u16x2 tp[kCL], sd[kCL];  // g + K - u (then d), g + u (then the "down" distance)
-      u16x2 pm = kNone2, sm = kNone2;
-#pragma unroll
-      for (int i = 0; i < kCL; ++i) {
-        const u16x2 g = __builtin_bit_cast(u16x2, g32[i * (kSP / 2)]);
-        const u16x2 uu = splat2(u0 + i);
-        tp[i] = __builtin_elementwise_sub_sat(__builtin_elementwise_add_sat(g, kRowOff2), uu);
-        sd[i] = __builtin_elementwise_add_sat(g, uu);
-        pm = __builtin_elementwise_min(pm, tp[i]);
-        sm = __builtin_elementwise_min(sm, sd[i]);
-      }
-      __syncthreads();  // every G read of the strip is done: the next row pass may write
-      // minima over the pair's chunks before / after this one (its 32 chunks
-      // are the lanes of one half wave)
-      u16x2 run, sfx;
-      if constexpr (kCh == 64) {
-        run = excl_prefix_min64(pm);
-        sfx = excl_suffix_min64(sm);
-      } else {
-        run = excl_prefix_min32(pm);
-        sfx = excl_suffix_min32(sm);
-      }
-      // suffix scan: the "down" distance min_{u'>=u} g(u') + u' - u
-#pragma unroll
-      for (int i = kCL - 1; i >= 0; --i) {
-        sfx = __builtin_elementwise_min(sfx, sd[i]);
-        sd[i] = __builtin_elementwise_sub_sat(sfx, splat2(u0 + i));
-      }
-      // prefix scan, d = min(up, down), the best (d << 16 | u) of each column
-      // over the chunk's grid rows (the last chunk's padding rows count 0)
-      uint32_t klo = 0, khi = 0;
-#pragma unroll
-      for (int i = 0; i < kCL; ++i) {
-        const u16x2 uu = splat2(u0 + i);
-        run = __builtin_elementwise_min(run, tp[i]);
-        const u16x2 up = __builtin_elementwise_sub_sat(__builtin_elementwise_add_sat(run, uu), kRowOff2);
-        const uint32_t d = __builtin_bit_cast(uint32_t, __builtin_elementwise_min(up, sd[i])) &
-                           (uint32_t)__builtin_amdgcn_sbfe((int)rowmask, i, 1);
-        tp[i] = __builtin_bit_cast(u16x2, d);
-        klo = max(klo, (d << 16) | (uint32_t)(u0 + i));
-        khi = max(khi, (d & 0xFFFF0000u) | (uint32_t)(u0 + i));
-      }
+      // ---- column pass: this thread's column pair and chunk of kCL rows
+      u16x2 tp[kCL];  // d of the chunk's cells
+      uint32_t klo, khi;
+      const int u0 = column_pass<kCL, kCh, kSP>(G, u0c, pair, rowmask, tp, klo, khi);
       const int v = c0 + 2 * pair;
       const int collect = thr >= 0 ? thr : cthr;
       // cells with d >= collect into the LDS list; an overflowed list (count
@@ -1195,14 +1272,7 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
         }
       }
       if (thr >= 0) return;
-      if (v < RY && klo > bestkey) {
-        bestkey = klo;
-        bestv = v;
-      }
-      if (v + 1 < RY && khi > bestkey) {
-        bestkey = khi;
-        bestv = v + 1;
-      }
+      best_update(klo, khi, v, RY, bestkey, bestv);
       if (s.dist_ch && st < kMaxTrack) {  // the strip's max(d), for the cache pass
         const uint32_t sm2 = wave_max_u32(max(v < RY ? klo >> 16 : 0u, v + 1 < RY ? khi >> 16 : 0u));
         if ((tid & 63) == 0) atomicMax(&s_smax[st], (int)sm2);
@@ -1211,7 +1281,7 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
       if (keep) {  // the target cells of this chunk's columns, from registers
         for (int t = 0; t < T; ++t) {
           int tu, tv;
-          target(t, tu, tv);
+          target_ext(t, px, py, pad, s.ego, E, tu, tv);
           if ((tv == v || tv == v + 1) && tu >= u0 && tu < u0 + kCL && tu < RX) {
             uint32_t val = 0;
 #pragma unroll
@@ -1221,7 +1291,7 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
         }
       }
     };
-    const int nstrips = (cov && !fast && mode != 3) ? nstrips_all : 0;
+    const int nstrips = (cov && !fast) ? nstrips_all : 0;
     // The cache's cells in the same pass: every cell with d >= M - kDistT
     // (M = the new max, known only at the end) has d >= any lower bound of
     // M, less kDistT.  Bounds: theta0 and the strips' maxima so far (s_smax
@@ -1286,40 +1356,30 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
     }
     DSTAMP(ts2);
     dist_reload(s, io);
-    const int vmax = bestv >= 0 ? (int)(bestkey >> 16) : -1;
-    const int ubest = (int)(bestkey & 0xFFFF), vbest = bestv;
-    // witness: of the maxima, the one farthest from the robot (new coverage
-    // comes from around the robot, so it keeps M valid longest)
-    if (!fast && cov && vmax >= 0) {
-      const int far = abs(ubest - (px + pad)) + abs(vbest - (py + pad));
-      // 16 bits per field: d, far, u, v are all < 65535 (mc_create bounds
-      // width + length + 4 pad), so wide grids keep an exact witness
-      atomicMax(&s_key, ((unsigned long long)vmax << 48) | ((unsigned long long)far << 32) |
-                            ((unsigned long long)ubest << 16) | (unsigned long long)vbest);
-    }
+    if (!fast && cov && bestv >= 0) publish_key(&s_key, bestkey, bestv, px, py, pad);
     __syncthreads();
     bool merged = false;  // this part finalises its split map (fused mode 2)
     if (mode == 2 && S > 1) {
       // ---- a part: publish the best key, the targets it holds (raw d in
       // the output buffers), its strips' maxima and its cache candidates;
-      // the part that finishes last (fused) or mode 3 finalises the map
+      // the part that finishes last finalises the map
       if (tid == 0 && s_key) atomicMax(s.dist_gkey + ea, s_key);
       for (int t = tid; t < T; t += kDtThreads)
         if (s_d[t] >= 0) {
-          if (t < 5) st_ho(pre_out + (size_t)ea * 8 + 1 + t, (float)s_d[t], true);
-          else st_ho(dist_obs + (size_t)ea * E * E + (t - 5), (float)s_d[t], true);
+          if (t < 5) st_sc1(pre_out + (size_t)ea * 8 + 1 + t, (float)s_d[t]);
+          else st_sc1(dist_obs + (size_t)ea * E * E + (t - 5), (float)s_d[t]);
         }
       for (int st = st_lo + tid; st < min(st_hi, kMaxTrack); st += kDtThreads)
-        if ((ran >> st) & 1ull) st_ho(s.dist_sm + (size_t)ea * kMaxTrack + st, (uint32_t)min(s_smax[st], 0xFFFF), true);
+        if ((ran >> st) & 1ull) st_sc1(s.dist_sm + (size_t)ea * kMaxTrack + st, (uint32_t)min(s_smax[st], 0xFFFF));
       if (theta0 > 0) {
         const int n = s_ccount;
         if (n > 0) {
           // this part's segment and count (kDistK + 1: overflowed)
           const size_t sg = (size_t)fi * kDistGParts + part;
-          if (tid == 0) st_ho(s.dist_gcnt + sg, (uint32_t)min(n, kDistK + 1), true);
+          if (tid == 0) st_sc1(s.dist_gcnt + sg, (uint32_t)min(n, kDistK + 1));
           if (n <= kDistK)
             for (int k = tid; k < n; k += kDtThreads)
-              st_ho(s.dist_gcand + sg * kDistK + k, make_int2(s_ccell[k], s_cdv[k]), true);
+              st_sc1(s.dist_gcand + sg * kDistK + k, make_int2(s_ccell[k], s_cdv[k]));
         }
       }
       // every storing wave's stores done, then one arrival per part: an
@@ -1339,11 +1399,11 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
       if (merged) {
         // the map's bitboard is staged here (every part stages it): a second
         // cache pass, if the parts' lists overflowed, needs no restaging
-        merge_parts(true);
+        merge_parts();
         cov = s_cov != 0;  // the map's, from the parts' keys
       }
 #ifdef MC_DIST_STAMPS
-      {  // a part (flag bit 52): stage, strips, publish (mode 3 leaves these)
+      {  // a part (flag bit 52): stage, strips, publish (the map's record below overwrites the merging part's)
         uint64_t tp = 0;
         DSTAMP(tp);
         if (tid == 0 && s.stamps && ea < (uint32_t)s.B * 16u) {
@@ -1384,15 +1444,12 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
     if (fast) {
       cache_serve<kDtThreads>(s, T, ea, s_fkey, ccnt, cM0, s_cdv, s_d, pre_out, dist_obs, count);
     } else {
-      if (tid == 0) {  // M unknown (-1) while nothing is covered: every step recomputes it
-        const int wu = (int)((s_key >> 16) & 0xFFFF), wv = (int)(s_key & 0xFFFF);
-        reinterpret_cast<int2*>(s.dist_mw)[ea] = make_int2(M, pack_witness(wu - pad, wv - pad));
-      }
+      if (tid == 0) write_map_mw(s, ea, pad, M, s_key);
       if (s.dist_ch) {
         // the cache pass: every cell with d >= M - kDistT (strips whose max
         // reaches it; the others only carry their last covered column)
         int cnt = -1;
-        // the main pass's list (mode 3: the parts' lists) holds them all
+        // the main pass's list (a merged map: the parts' lists) holds them all
         const bool main_ok = theta0 > 0 && s_ccount <= kDistK;
         if (cov && M >= 0 && main_ok) {
           const int thr = M - kDistT, n = s_ccount;
@@ -1406,7 +1463,6 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
           cnt = s_kept;
           dflags |= 1ull << 49;
         } else if (cov && M >= 0) {
-          if (idle) stage_cb();
           dflags |= 1ull << 50;
           __syncthreads();  // every thread has read s_ccount
           if (tid == 0) s_ccount = 0;
@@ -1440,19 +1496,10 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
         }
       }
     }
-    if (!fast) {
-      if (post) {
-        float* dst = dist_obs + (size_t)ea * E * E;
-        for (int t = 5 + tid; t < T; t += kDtThreads)
-          dst[t - 5] = dist_value((float)(cov ? s_d[t] : -1), Mf);
-      }
-      float* pd = pre_out + (size_t)ea * 8;
-      if (tid == 0) pd[0] = Mf;
-      if (tid < 5) pd[1 + tid] = (float)(cov ? s_d[tid] : -1);
-    }
+    if (!fast) write_map_terms<kDtThreads>(tid, ea, post, T, E, cov, Mf, s_d, pre_out, dist_obs);
     DSTAMP(ts3);
 #ifdef MC_DIST_STAMPS
-    if (tid == 0 && s.stamps && ea < (uint32_t)s.B * 16u && mode != 3) {
+    if (tid == 0 && s.stamps && ea < (uint32_t)s.B * 16u) {
       auto f16 = [](uint64_t a, uint64_t b) -> uint64_t {
         const uint64_t d = (b - a) >> 4;
         return d < 0xFFFFull ? d : 0xFFFFull;
@@ -1471,38 +1518,8 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
 #endif
     __syncthreads();  // the LDS is reused by the next item
   }
-  // the shards' counts (State::dist_shc) = entries, count[1] = workgroups
-  // done: the last workgroup to finish zeroes them for the next step's env kernel (every workgroup has
-  // read the entry count before it counts itself done; no memset launch per
-  // step) and keeps the entry count in count[2] (MC_FIELD_DIST_LISTED); the
-  // cache hits count[3] go to count[4] the same way (MC_FIELD_DIST_CACHED)
-  if (list && threadIdx.x == 0) {
-    uint32_t* cnt = count;
-    if (n_items == 0) {
-      if (blockIdx.x == 0) {
-        cnt[2] = cnt[4] = 0;
-        if (s.dist_tot) s.dist_tot[3] += 1ull;
-      }
-    } else {
-      __threadfence();
-      if (atomicAdd(cnt + 1, 1u) == gridDim.x - 1) {
-        uint32_t nl = 0;
-        for (int k = 0; k < kListShards; ++k) nl += atomicExch(s.dist_shc + k * kShardStride, 0u);
-        const uint32_t nh = atomicExch(cnt + 3, 0u);
-        atomicExch(cnt + 2, nl);
-        atomicExch(cnt + 4, nh);
-        atomicExch(cnt + 1, 0u);
-        if (s.dist_tot) {  // MC_FIELD_DIST_TOTALS: the cache hits were served
-          s.dist_tot[0] += nl;
-          s.dist_tot[1] += nh;
-          s.dist_tot[2] += nl - nh;
-          s.dist_tot[3] += 1ull;
-        }
-      }
-    }
-  }
+  if (list && threadIdx.x == 0) list_done(s, count, n_items);
 }
-
 
 // static LDS of dist_kernel_t beyond dist_lds_bytes: the top-cell cache list
 // (kDistK cells and d), the strip maxima and the scalars
@@ -1685,8 +1702,10 @@ static hipError_t launch_full(const State& s, int pad, int post, float* pre_out,
 // strip, so this kernel keeps only two 64-column word columns of the map in
 // LDS at a time and, per row and word column, the first covered column at or
 // right of it (`nxt`, built right to left first: the row pass's nearest
-// covered cell right of a strip).  Same strips, same row and column passes
-// (a wave of 64 row chunks per column pair), same outputs as mode 0 of
+// covered cell right of a strip).  Same strips, the row pass written out as
+// dist_kernel_t's, and that kernel's functions for the rest (column_pass with
+// a wave of 64 row chunks per column pair, best_update, target_ext,
+// publish_key, write_map_*, list_done); same outputs as mode 0 of
 // dist_kernel_t without the top-cell cache (mc_create leaves the cache off
 // for these maps).  One workgroup of 1,024 threads per listed map (or per map
 // with list == nullptr), one per CU (LDS).
@@ -1719,31 +1738,12 @@ __device__ __forceinline__ void big_stage_word(const State& s, const uint64_t* f
   const int RWm = (s.TC + 7) >> 3;
   for (int ti = opaque_tid(); ti < s.TR; ti += kBigThreads) {
     uint32_t lo[8], hi[8];
-#pragma unroll
-    for (int j = 0; j < 8; j += 2) {
-      const int tj = 8 * q + j;
-      uint4 t = make_uint4(0u, 0u, 0u, 0u);
-      if (q >= 0 && q < RWm && tj < s.TC) t = *reinterpret_cast<const uint4*>(free_t + tile_index(s.TCS, ti, tj));
-      if (tj + 1 >= s.TC) t.z = t.w = 0u;
-      lo[j] = t.x;
-      hi[j] = t.y;
-      lo[j + 1] = t.z;
-      hi[j + 1] = t.w;
-    }
+    load_tile_row8(s, free_t, ti, q, q >= 0 && q < RWm, lo, hi);
     const int nr = min(8, s.Wp - 8 * ti);
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
       if (r >= nr) break;
-      const uint32_t* src = r < 4 ? lo : hi;
-      const uint32_t b = (uint32_t)(r & 3);
-      const uint32_t sel2 = b | ((4u + b) << 8) | 0x0C0C0000u;
-      const uint32_t p01 = __builtin_amdgcn_perm(src[1], src[0], sel2);
-      const uint32_t p23 = __builtin_amdgcn_perm(src[3], src[2], sel2);
-      const uint32_t p45 = __builtin_amdgcn_perm(src[5], src[4], sel2);
-      const uint32_t p67 = __builtin_amdgcn_perm(src[7], src[6], sel2);
-      const uint32_t wlo = __builtin_amdgcn_perm(p23, p01, 0x05040100u);
-      const uint32_t whi = __builtin_amdgcn_perm(p67, p45, 0x05040100u);
-      wc[8 * ti + r] = (uint64_t)wlo | ((uint64_t)whi << 32);
+      wc[8 * ti + r] = tile_row_word(lo, hi, r);
     }
   }
 }
@@ -1775,16 +1775,6 @@ __global__ __launch_bounds__(kBigThreads, 1) void dist_big_kernel(State s, int p
     const uint64_t* free_t = s.freem + (size_t)ea * s.MT;
     const int2 pp = reinterpret_cast<const int2*>(s.pos)[ea];
     const int px = pp.x, py = pp.y;
-    auto target = [&](int t, int& u, int& v) {  // as dist_kernel_t (extended coordinates)
-      if (t >= 5) {
-        const int r = (t - 5) / E, c = (t - 5) - r * E;
-        u = px + pad - s.ego + r;
-        v = py + pad - s.ego + c;
-      } else {
-        u = px + (t == 1 ? 1 : (t == 3 ? -1 : 0));
-        v = py + (t == 2 ? 1 : (t == 4 ? -1 : 0));
-      }
-    };
     for (int t = tid; t < T; t += kBigThreads) s_d[t] = -1;
     if (tid == 0) {
       s_key = 0;
@@ -1833,6 +1823,7 @@ __global__ __launch_bounds__(kBigThreads, 1) void dist_big_kernel(State s, int p
       }
       const int off = m0 - 64 * q0;  // 0..63
       // ---- row pass: g of the strip's 32 cells of each row, 16 u16 pairs
+      // (from `lc` on as dist_kernel_t's: change both)
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int u = tid + h * kBigThreads;
@@ -1840,8 +1831,7 @@ __global__ __launch_bounds__(kBigThreads, 1) void dist_big_kernel(State s, int p
         uint2* grow = reinterpret_cast<uint2*>(G + u * kBigSP);
         const int X = u - pad;
         if (u >= RX || X < 0 || X >= s.Wp) {  // padding rows / the pad ring: no covered cell
-#pragma unroll
-          for (int k = 0; k < 8; ++k) grow[k] = make_uint2(~0u, ~0u);
+          row_pass_none(grow);
           continue;
         }
         const uint64_t wlo = q0 >= 0 ? wc[(size_t)(q0 & 1) * s.Wp + X] : 0ull;
@@ -1900,54 +1890,17 @@ __global__ __launch_bounds__(kBigThreads, 1) void dist_big_kernel(State s, int p
         }
       }
       __syncthreads();
-      // ---- column pass (as dist_kernel_t's, 64 chunks of a column pair per wave)
-      int u0 = u0c;
-      asm volatile("" : "+v"(u0));
-      const uint32_t* g32 = reinterpret_cast<const uint32_t*>(G) + u0 * (kBigSP / 2) + pair;
-      u16x2 tp[kBigCL], sd[kBigCL];
-      u16x2 pm = kNone2, sm = kNone2;
-#pragma unroll
-      for (int i = 0; i < kBigCL; ++i) {
-        const u16x2 g = __builtin_bit_cast(u16x2, g32[i * (kBigSP / 2)]);
-        const u16x2 uu = splat2(u0 + i);
-        tp[i] = __builtin_elementwise_sub_sat(__builtin_elementwise_add_sat(g, kRowOff2), uu);
-        sd[i] = __builtin_elementwise_add_sat(g, uu);
-        pm = __builtin_elementwise_min(pm, tp[i]);
-        sm = __builtin_elementwise_min(sm, sd[i]);
-      }
-      __syncthreads();  // every G read of the strip is done: the next row pass may write
-      u16x2 run = excl_prefix_min64(pm), sfx = excl_suffix_min64(sm);
-#pragma unroll
-      for (int i = kBigCL - 1; i >= 0; --i) {
-        sfx = __builtin_elementwise_min(sfx, sd[i]);
-        sd[i] = __builtin_elementwise_sub_sat(sfx, splat2(u0 + i));
-      }
-      uint32_t klo = 0, khi = 0;
-#pragma unroll
-      for (int i = 0; i < kBigCL; ++i) {
-        const u16x2 uu = splat2(u0 + i);
-        run = __builtin_elementwise_min(run, tp[i]);
-        const u16x2 up = __builtin_elementwise_sub_sat(__builtin_elementwise_add_sat(run, uu), kRowOff2);
-        const uint32_t d = __builtin_bit_cast(uint32_t, __builtin_elementwise_min(up, sd[i])) &
-                           (uint32_t)__builtin_amdgcn_sbfe((int)rowmask, i, 1);
-        tp[i] = __builtin_bit_cast(u16x2, d);
-        klo = max(klo, (d << 16) | (uint32_t)(u0 + i));
-        khi = max(khi, (d & 0xFFFF0000u) | (uint32_t)(u0 + i));
-      }
+      // ---- column pass: 64 chunks of a column pair per wave
+      u16x2 tp[kBigCL];
+      uint32_t klo, khi;
+      const int u0 = column_pass<kBigCL, kBigCh, kBigSP>(G, u0c, pair, rowmask, tp, klo, khi);
       const int v = c0 + 2 * pair;
-      if (v < RY && klo > bestkey) {
-        bestkey = klo;
-        bestv = v;
-      }
-      if (v + 1 < RY && khi > bestkey) {
-        bestkey = khi;
-        bestv = v + 1;
-      }
+      best_update(klo, khi, v, RY, bestkey, bestv);
       const bool keep = v + 1 >= tv_lo && v <= tv_hi && u0 + kBigCL > tu_lo && u0 <= tu_hi;
-      if (keep) {
+      if (keep) {  // the target cells of this chunk's columns, from registers
         for (int t = 0; t < T; ++t) {
           int tu, tv;
-          target(t, tu, tv);
+          target_ext(t, px, py, pad, s.ego, E, tu, tv);
           if ((tv == v || tv == v + 1) && tu >= u0 && tu < u0 + kBigCL && tu < RX) {
             uint32_t val = 0;
 #pragma unroll
@@ -1957,55 +1910,14 @@ __global__ __launch_bounds__(kBigThreads, 1) void dist_big_kernel(State s, int p
         }
       }
     }
-    const int vmax = bestv >= 0 ? (int)(bestkey >> 16) : -1;
-    if (cov && vmax >= 0) {
-      const int ubest = (int)(bestkey & 0xFFFF), vbest = bestv;
-      const int far = abs(ubest - (px + pad)) + abs(vbest - (py + pad));
-      atomicMax(&s_key, ((unsigned long long)vmax << 48) | ((unsigned long long)far << 32) |
-                            ((unsigned long long)ubest << 16) | (unsigned long long)vbest);
-    }
+    if (cov && bestv >= 0) publish_key(&s_key, bestkey, bestv, px, py, pad);
     __syncthreads();
     const int M = cov ? (int)(s_key >> 48) : -1;
-    const float Mf = (float)M;
-    if (tid == 0) {
-      const int wu = (int)((s_key >> 16) & 0xFFFF), wv = (int)(s_key & 0xFFFF);
-      reinterpret_cast<int2*>(s.dist_mw)[ea] = make_int2(M, pack_witness(wu - pad, wv - pad));
-    }
-    if (post) {
-      float* dst = dist_obs + (size_t)ea * E * E;
-      for (int t = 5 + tid; t < T; t += kBigThreads) dst[t - 5] = dist_value((float)(cov ? s_d[t] : -1), Mf);
-    }
-    float* pd = pre_out + (size_t)ea * 8;
-    if (tid == 0) pd[0] = Mf;
-    if (tid < 5) pd[1 + tid] = (float)(cov ? s_d[tid] : -1);
+    if (tid == 0) write_map_mw(s, ea, pad, M, s_key);
+    write_map_terms<kBigThreads>(tid, ea, post, T, E, cov, (float)M, s_d, pre_out, dist_obs);
     __syncthreads();  // the LDS is reused by the next item
   }
-  // the work list's bookkeeping, as dist_kernel_t's (mode 0 with a list)
-  if (list && threadIdx.x == 0) {
-    uint32_t* cnt = count;
-    if (n_items == 0) {
-      if (blockIdx.x == 0) {
-        cnt[2] = cnt[4] = 0;
-        if (s.dist_tot) s.dist_tot[3] += 1ull;
-      }
-    } else {
-      __threadfence();
-      if (atomicAdd(cnt + 1, 1u) == gridDim.x - 1) {
-        uint32_t nl = 0;
-        for (int k = 0; k < kListShards; ++k) nl += atomicExch(s.dist_shc + k * kShardStride, 0u);
-        const uint32_t nh = atomicExch(cnt + 3, 0u);
-        atomicExch(cnt + 2, nl);
-        atomicExch(cnt + 4, nh);
-        atomicExch(cnt + 1, 0u);
-        if (s.dist_tot) {
-          s.dist_tot[0] += nl;
-          s.dist_tot[1] += nh;
-          s.dist_tot[2] += nl - nh;
-          s.dist_tot[3] += 1ull;
-        }
-      }
-    }
-  }
+  if (list && threadIdx.x == 0) list_done(s, count, n_items);
 }
 
 static hipError_t launch_big(const State& s, int pad, int post, float* pre_out, float* dist_obs,

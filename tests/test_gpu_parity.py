@@ -202,6 +202,12 @@ BATCH_CASES = {
     "minimap_dist_dijkstra": (base_cfg(numrobot=2, mini_map_rad=7, dist_reward=1, dijkstra_input=1,
                                        sensor_config={"num_lasers": 11, "range": 4}),
                               lambda rs: tri(rs, 30, 30), 6, 30),
+    # pad = mini_map_rad = 17 > 16: the transform stages its bitboard in two
+    # passes (map rows, then the funnel shift by pad); the 58 x 104 extended
+    # grid has two words per row, so the shift crosses a word boundary
+    "minimap_dist_pad17": (base_cfg(numrobot=2, mini_map_rad=17, dist_reward=1,
+                                    sensor_config={"num_lasers": 9, "range": 4}),
+                           lambda rs: bern(rs, 24, 70, 0.1), 4, 12),
     "minimap_upscale": (base_cfg(numrobot=2, egoradius=4, mini_map_rad=2, sensor_type="square_sensor",
                                  sensor_config={"range": 1}), lambda rs: bern(rs, 20, 20, 0.1), 6, 30),
     "minimap_equal_sizes": (base_cfg(numrobot=2, egoradius=3, mini_map_rad=3), lambda rs: bern(rs, 24, 24, 0.1),
