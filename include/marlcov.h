@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define MARLCOV_ABI_VERSION 10
+#define MARLCOV_ABI_VERSION 11
 
 enum {
   MC_OK = 0,
@@ -279,7 +279,49 @@ int mc_set_dist_obs(void* env, float* dev_dist_obs);
  * dist / dijkstra layer in the reference).  Required before the first reset. */
 int mc_set_minimap_obs(void* env, double* dev_minimap_obs);
 
-/* Synchronise `stream` and report (then clear) the device error word. */
+/* Fork / restore env state on the device (ABI v11).  Env e of `dst` takes the
+ * complete state of env dev_src[e] of `src` (dev_src: int32 [dst.num_envs],
+ * device; -1 = leave env e as it is): after the call env e is
+ * indistinguishable from its source in every later mc_step, mc_reset,
+ * mc_get_state and episode record.  Copied per env: the env record (counters,
+ * done_thresh, currstep, moved, env_grid, episode), POS, FREE, OBST, VISITED,
+ * EP_PC / EP_LEN and, with dist_reward, DIST_MW, the PRE distance terms and
+ * the top-cell cache -- derived state is copied, not invalidated, and the
+ * destination recomputes its PRE terms at the next step only if either handle
+ * would have.  The start-cell stream stays keyed by the destination's own
+ * global env id (env_offset + e) and the copied episode count.
+ *
+ * Handles.  `src` may be `dst` or another handle on the same HIP device with
+ * the same num_agents, width, length, pad and num_grids, dist_reward on or off
+ * alike and the top-cell cache present or absent alike (mc_sg_copy_envs: the
+ * same num_agents, width, length, num_grids, use_scanning, dist_reward, and
+ * state buffers registered alike).  Anything else returns MC_EINVAL, the
+ * message names the first field that differs, and nothing is enqueued.
+ * num_envs, auto_reset, maxsteps, seed, the offsets and the penalties may
+ * differ.  env_grid is copied as an index: the caller keeps the two grid
+ * pools equal.
+ *
+ * Call contract.  Stream-ordered and asynchronous; one kernel launch; no
+ * allocation, no synchronisation and no host read (capturable in a graph);
+ * needs neither grids nor a beam table to be set.
+ *
+ * Checked on the device, before any load through the index: an index outside
+ * [-1, src.num_envs) is an error; and when src == dst, a source env s named by
+ * another env must keep itself (dev_src[s] is -1 or s), so a fork reads only
+ * envs the same call does not write -- chains and permutations within one
+ * handle are errors.  The offending destination env is left untouched, every
+ * valid entry of the same call is still applied, and the device error word
+ * gets bit 32 (mc_check / mc_sg_check report it).
+ *
+ * mc_sg_copy_envs copies POS, COVERED, OBST, COV_COUNT, CURRSTEP, DONE_THRESH,
+ * A_PREV, ENV_GRID, EPISODE, EP_PC / EP_LEN, the distance layer's max and the
+ * env's slices of the registered state buffers (planes and dist), which the
+ * caller can read at once. */
+int mc_copy_envs(void* dst, void* src, const int32_t* dev_src, void* stream);
+
+/* Synchronise `stream` and report (then clear) the device error word:
+ * 1 = window, 4 = placement failed, 8 = bad injected cell, 32 = mc_copy_envs
+ * index. */
 int mc_check(void* env, void* stream);
 
 /* ==========================================================================
@@ -381,8 +423,11 @@ int64_t mc_sg_field_bytes(void* env, int32_t field);
 int mc_sg_get_state(void* env, int32_t field, void* dev_dst, int64_t bytes, void* stream);
 /* Uploads mark the state buffers for a full rewrite at the next call. */
 int mc_sg_set_state(void* env, int32_t field, const void* dev_src, int64_t bytes, void* stream);
+/* mc_copy_envs for SuperGridRL handles (rules and field list there). */
+int mc_sg_copy_envs(void* dst, void* src, const int32_t* dev_src, void* stream);
 /* Synchronise and report (then clear) the device error word:
- * 4 = placement failed, 8 = bad injected cell, 16 = motion_penalty KeyError. */
+ * 4 = placement failed, 8 = bad injected cell, 16 = motion_penalty KeyError,
+ * 32 = mc_sg_copy_envs index. */
 int mc_sg_check(void* env, void* stream);
 
 /* Diagnostics: in a -DMC_STAMPS build, record per-phase s_memtime stamps of

@@ -8,10 +8,11 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libmarlcov.so")
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 MC_OK, MC_EINVAL, MC_EHIP, MC_ESTATE, MC_EDEVICE = 0, -1, -2, -3, -4
 SENSOR_LIDAR, SENSOR_SQUARE = 0, 1
@@ -142,6 +143,7 @@ SIGNATURES = [
     ("mc_field_bytes", _I64, [_VP, _I32]),
     ("mc_get_state", ctypes.c_int, [_VP, _I32, _VP, _I64, _VP]),
     ("mc_set_state", ctypes.c_int, [_VP, _I32, _VP, _I64, _VP]),
+    ("mc_copy_envs", ctypes.c_int, [_VP, _VP, _VP, _VP]),
     ("mc_check", ctypes.c_int, [_VP, _VP]),
     ("mc_debug_stamps", ctypes.c_int, [_VP, _VP]),
     ("mc_set_dist_obs", ctypes.c_int, [_VP, _VP]),
@@ -158,6 +160,7 @@ SIGNATURES = [
     ("mc_sg_field_bytes", _I64, [_VP, _I32]),
     ("mc_sg_get_state", ctypes.c_int, [_VP, _I32, _VP, _I64, _VP]),
     ("mc_sg_set_state", ctypes.c_int, [_VP, _I32, _VP, _I64, _VP]),
+    ("mc_sg_copy_envs", ctypes.c_int, [_VP, _VP, _VP, _VP]),
     ("mc_sg_check", ctypes.c_int, [_VP, _VP]),
 ]
 
@@ -192,8 +195,14 @@ def load(path: str | None = None):
     return lib
 
 
+ERR_FORK = 1 << 5  # device error bit of mc_copy_envs / mc_sg_copy_envs (a bad or chained index)
+
+
 def check(rc: int, what: str = ""):
     if rc != MC_OK:
         msg = _lib.mc_last_error().decode(errors="replace") if _lib is not None else ""
+        word = re.search(r"error word 0x([0-9a-fA-F]+)", msg)
+        if rc == MC_EDEVICE and word and int(word.group(1), 16) & ERR_FORK:
+            msg += ": a fork index was outside [-1, source num_envs) or named an env the same call overwrites"
         raise MarlcovError(f"{what} failed ({rc}): {msg}")
     return rc

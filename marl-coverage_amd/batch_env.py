@@ -137,6 +137,9 @@ class BatchCoverageEnv:
         c.grid_offset = int(env_offset if grid_offset is None else grid_offset)
         self.env_offset = c.env_offset
         self._cfg = c
+        # what sibling() passes on to the new env
+        self._ctor = dict(device=dev, seed=seed, reset_grid_mode=reset_grid_mode, sensor=self.sensor,
+                          want_adjacency=want_adjacency, env_offset=env_offset, grid_offset=grid_offset)
 
         handle = ctypes.c_void_p()
         _lib.check(self.lib.mc_create(ctypes.byref(c), dev.index, ctypes.byref(handle)), "mc_create")
@@ -371,6 +374,49 @@ class BatchCoverageEnv:
         nbytes = t.numel() * t.element_size()
         _lib.check(self.lib.mc_set_state(self._h, field, t.data_ptr(), nbytes, self._stream()),
                    "mc_set_state")
+
+    # ------------------------------------------------------------------
+    def _fork_index(self, src_index, source):
+        """fork()'s arguments, checked: the int32 [B] device index tensor."""
+        torch = self._torch
+        if type(source) is not type(self):
+            raise ValueError(f"fork: source must be a {type(self).__name__}, got {type(source).__name__}")
+        if source.device != self.device:
+            raise ValueError(f"fork: source is on {source.device}, this env on {self.device}")
+        idx = src_index if isinstance(src_index, torch.Tensor) else torch.as_tensor(np.asarray(src_index))
+        if idx.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+            raise ValueError(f"fork: src_index must hold integers, got {idx.dtype}")
+        if tuple(idx.shape) != (self.num_envs,):
+            raise ValueError(f"fork: src_index must have shape [{self.num_envs}], got {list(idx.shape)}")
+        return idx.to(device=self.device, dtype=torch.int32).contiguous()
+
+    def fork(self, src_index, source=None):
+        """Env e takes the complete state of env ``src_index[e]`` of ``source``
+        (default: this env; -1 = env e stays as it is) in one launch
+        (mc_copy_envs): maps, positions, counters, episode record and, with
+        dist_reward, the distance terms and caches.  ``source`` is another
+        BatchCoverageEnv of the same shape on the same device (``sibling``).
+        Within one env a source env must keep itself (no chains); a bad index
+        leaves its env untouched and makes ``check()`` raise.  The output
+        tensors are not touched: ``reset(env_mask=zeros)`` rewrites them for
+        the current state."""
+        source = self if source is None else source
+        idx = self._fork_index(src_index, source)
+        _lib.check(self.lib.mc_copy_envs(self._h, source._h, idx.data_ptr(), self._stream()), "mc_copy_envs")
+
+    def sibling(self, num_envs, **overrides):
+        """A new env of ``num_envs`` envs that ``fork`` can copy to and from:
+        the same env_config, sensor (and beam table) and grid pool (copied on
+        the device), ``auto_reset`` off unless overridden, reset once.  The
+        snapshot store and the rollout scratch of model rollouts."""
+        kw = dict(self._ctor, auto_reset=False)
+        kw.update(overrides)
+        gen = dict(width=self.width - 2, length=self.length - 2, prob_obst=0.0, num_grids=self.num_grids)
+        sib = type(self)(self.config, num_envs, gen=gen, **kw)
+        for f in (_lib.FIELD_GRID_NEG, _lib.FIELD_GRID_POS, _lib.FIELD_NUMFREE):
+            sib.set_state(f, self.get_state(f))
+        sib.reset()
+        return sib
 
     def percent_covered(self):
         """float64 [B]: count_nonzero(_free_pad > 0) / count_nonzero(grid > 0)

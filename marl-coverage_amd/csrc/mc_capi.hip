@@ -15,6 +15,7 @@
 
 #include "marlcov.h"
 #include "mc_internal.h"
+#include "mc_fork.h"
 
 namespace mc {
 hipError_t launch_env(const State& s, int mode, const uint8_t* actions, const uint8_t* env_mask,
@@ -1092,6 +1093,52 @@ int mc_set_state(void* env, int32_t f, const void* dev_src, int64_t bytes, void*
   return MC_OK;
 }
 
+int mc_copy_envs(void* dst, void* src, const int32_t* dev_src, void* stream) {
+  Env* D = as_env(dst);
+  Env* S = as_env(src);
+  if (!D || !S || !dev_src) return fail(MC_EINVAL, "mc_copy_envs: null argument");
+  const mc::State& d = D->s;
+  const mc::State& s = S->s;
+  if (S != D) {
+    if (S->device != D->device)
+      return fail(MC_EINVAL, "mc_copy_envs: handles on HIP devices %d and %d", D->device, S->device);
+#define MC_SAME(what, a, b) \
+  if ((a) != (b)) return fail(MC_EINVAL, "mc_copy_envs: %s differs (%d vs %d)", what, (int)(a), (int)(b))
+    MC_SAME("num_agents", d.N, s.N);
+    MC_SAME("width", d.Wp, s.Wp);
+    MC_SAME("length", d.Lp, s.Lp);
+    MC_SAME("pad", d.pad, s.pad);
+    MC_SAME("num_grids", d.G, s.G);
+    MC_SAME("dist_reward", d.dist_mw != nullptr, s.dist_mw != nullptr);
+    MC_SAME("top-cell cache", d.dist_cc != nullptr, s.dist_cc != nullptr);
+#undef MC_SAME
+  }
+  // Every per-env array that holds state between two calls.  The step's work
+  // lists (dist_cnt / dist_shc, dist_full, dist_gkey, dist_gcnt, dist_pcnt,
+  // dist_rmask, dj_list, the HBM dijkstra scratch) are filled and consumed
+  // inside one mc_step / mc_reset and carry nothing over.
+  const size_t N = d.N, mw = (size_t)d.MT;
+  mc::ForkTable t;
+  t.add(s.freem, d.freem, N * mw * 8);
+  t.add(s.obstm, d.obstm, N * mw * 8);
+  t.add(s.vis, d.vis, mw * 8);
+  t.add(s.dist_cc, d.dist_cc, N * mc::kDistK * 4);
+  t.add(s.dist_cd, d.dist_cd, N * mc::kDistK * 4);
+  t.add(s.dist_sm, d.dist_sm, N * mc::kDistStrips * 4);
+  t.add(s.dist_ch, d.dist_ch, N * 32);
+  t.add(S->dist_pre, D->dist_pre, N * 8 * sizeof(float));
+  t.add(s.dist_mw, d.dist_mw, N * 8);
+  t.add(s.rec, d.rec, sizeof(mc::EnvRec));
+  t.add(s.pos, d.pos, N * 8);
+  t.add(s.ep_pc, d.ep_pc, 8);
+  t.add(s.ep_len, d.ep_len, 4);
+  HIP_TRY(hipSetDevice(D->device));
+  HIP_TRY(mc::launch_fork(t, dev_src, s.B, d.B, S == D, d.err, mc::ERR_FORK, (hipStream_t)stream));
+  // a fork sends no map to a transform that its source would not send
+  D->dist_pre_stale = D->dist_pre_stale || S->dist_pre_stale;
+  return MC_OK;
+}
+
 int mc_set_dist_obs(void* env, float* dev_dist_obs) {
   Env* E = as_env(env);
   if (!E || !dev_dist_obs) return fail(MC_EINVAL, "mc_set_dist_obs: null argument");
@@ -1133,7 +1180,7 @@ int mc_check(void* env, void* stream) {
   if (err) {
     HIP_TRY(hipMemsetAsync(E->s.err, 0, 4, st));
     HIP_TRY(hipStreamSynchronize(st));
-    return fail(MC_EDEVICE, "device error word 0x%x (1=window 4=placement 8=inject)", err);
+    return fail(MC_EDEVICE, "device error word 0x%x (1=window 4=placement 8=inject 32=copy_envs index)", err);
   }
   return MC_OK;
 }

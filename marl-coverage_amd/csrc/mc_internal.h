@@ -17,6 +17,8 @@ enum : uint32_t {
                             // every lidar cell is within Chebyshev ceil(range))
   ERR_PLACEMENT = 1u << 2,  // could not place all robots on free cells
   ERR_INJECT = 1u << 3,     // injected start cell invalid (obstacle / clash)
+  ERR_FORK = 1u << 5,       // mc_copy_envs: index out of range, or a source env
+                            // that the same call overwrites (mc_fork.hip)
 };
 
 // One lidar beam, derived on the host from the reference's (xinc, yinc,

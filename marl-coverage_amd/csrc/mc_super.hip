@@ -39,6 +39,7 @@
 
 #include "marlcov.h"
 #include "mc_device.h"
+#include "mc_fork.h"
 
 namespace mc {
 void set_last_error(const char* msg);
@@ -51,7 +52,12 @@ using mc::dist_value;
 using mc::low_mask;
 using mc::philox;
 
-enum : uint32_t { ERR_PLACEMENT = 1u << 2, ERR_INJECT = 1u << 3, ERR_KEY = 1u << 4 };
+enum : uint32_t {
+  ERR_PLACEMENT = 1u << 2,
+  ERR_INJECT = 1u << 3,
+  ERR_KEY = 1u << 4,
+  ERR_FORK = 1u << 5,  // mc_sg_copy_envs: bad index or a source env the call overwrites (mc_fork.hip)
+};
 constexpr int kMaxAgents = 64;
 constexpr int kMaxRadius = 15;   // a window row (2r+1 cells) fits 32 bits
 constexpr int kMaxSide = 4096;
@@ -1627,6 +1633,49 @@ int mc_sg_set_state(void* env, int32_t f, const void* dev_src, int64_t bytes, vo
   return MC_OK;
 }
 
+int mc_sg_copy_envs(void* dst, void* src, const int32_t* dev_src, void* stream) {
+  SgEnv* D = as_sg(dst);
+  SgEnv* S = as_sg(src);
+  if (!D || !S || !dev_src) return sg_fail(MC_EINVAL, "mc_sg_copy_envs: null argument");
+  const mcs::SState& d = D->s;
+  const mcs::SState& s = S->s;
+  if (S != D) {
+    if (S->device != D->device)
+      return sg_fail(MC_EINVAL, "mc_sg_copy_envs: handles on HIP devices %d and %d", D->device, S->device);
+#define SG_SAME(what, a, b) \
+  if ((a) != (b)) return sg_fail(MC_EINVAL, "mc_sg_copy_envs: %s differs (%d vs %d)", what, (int)(a), (int)(b))
+    SG_SAME("num_agents", d.N, s.N);
+    SG_SAME("width", d.W, s.W);
+    SG_SAME("length", d.L, s.L);
+    SG_SAME("num_grids", d.G, s.G);
+    SG_SAME("use_scanning", d.scan, s.scan);
+    SG_SAME("dist_reward", d.dist, s.dist);
+    SG_SAME("registered buffers (mc_sg_set_obs)", d.planes != nullptr, s.planes != nullptr);
+#undef SG_SAME
+  }
+  const size_t N = d.N, mw = (size_t)d.W * d.RW, cells = (size_t)d.W * d.L;
+  mc::ForkTable t;
+  t.add(s.cov, d.cov, mw * 8);
+  t.add(s.obst, d.obst, mw * 8);
+  t.add(s.planes, d.planes, (size_t)(d.P + 2) * cells);
+  t.add(s.dist_plane, d.dist_plane, cells * 4);
+  t.add(s.pos, d.pos, N * 8);
+  t.add(s.done_thresh, d.done_thresh, 8);
+  t.add(s.ep_pc, d.ep_pc, 8);
+  t.add(s.cov_cnt, d.cov_cnt, 4);
+  t.add(s.currstep, d.currstep, 4);
+  t.add(s.a_prev, d.a_prev, 4);
+  t.add(s.env_grid, d.env_grid, 4);
+  t.add(s.episode, d.episode, 4);
+  t.add(s.ep_len, d.ep_len, 4);
+  t.add(s.dist_M, d.dist_M, 4);
+  t.add(s.full, d.full, 1);
+  SG_TRY(hipSetDevice(D->device));
+  SG_TRY(mc::launch_fork(t, dev_src, s.B, d.B, S == D, d.err, mcs::ERR_FORK, (hipStream_t)stream));
+  D->stale = D->stale || S->stale;  // never more transforms than the source would run
+  return MC_OK;
+}
+
 int mc_sg_check(void* env, void* stream) {
   SgEnv* E = as_sg(env);
   if (!E) return sg_fail(MC_EINVAL, "mc_sg_check: null env");
@@ -1638,7 +1687,8 @@ int mc_sg_check(void* env, void* stream) {
   if (err) {
     SG_TRY(hipMemsetAsync(E->s.err, 0, 4, st));
     SG_TRY(hipStreamSynchronize(st));
-    return sg_fail(MC_EDEVICE, "device error word 0x%x (4=placement 8=inject 16=motion_penalty KeyError)", err);
+    return sg_fail(MC_EDEVICE,
+                   "device error word 0x%x (4=placement 8=inject 16=motion_penalty KeyError 32=copy_envs index)", err);
   }
   return MC_OK;
 }

@@ -16,7 +16,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .batch_env import grid_to_int8
+from .batch_env import BatchCoverageEnv, grid_to_int8
 
 _SG_DTYPES = {
     _lib.SG_FIELD_POS: "int32", _lib.SG_FIELD_COVERED: "int64", _lib.SG_FIELD_OBST: "int64",
@@ -107,6 +107,9 @@ class BatchSuperGridEnv:
         c.env_offset = int(env_offset)  # global ids (BatchCoverageEnv)
         c.grid_offset = int(env_offset if grid_offset is None else grid_offset)
         self._cfg = c
+        # what sibling() passes on to the new env
+        self._ctor = dict(device=dev, seed=seed, maxsteps=maxsteps, reset_grid_mode=reset_grid_mode,
+                          env_offset=env_offset, grid_offset=grid_offset)
         h = ctypes.c_void_p()
         _lib.check(self.lib.mc_sg_create(ctypes.byref(c), dev.index, ctypes.byref(h)), "mc_sg_create")
         self._h = h
@@ -221,6 +224,32 @@ class BatchSuperGridEnv:
             raise ValueError(f"field {field} must have shape {self.field_shape(field)}")
         _lib.check(self.lib.mc_sg_set_state(self._h, field, t.data_ptr(), t.numel() * t.element_size(),
                                             self._stream()), "mc_sg_set_state")
+
+    _fork_index = BatchCoverageEnv._fork_index
+
+    def fork(self, src_index, source=None):
+        """Env e takes the complete state of env ``src_index[e]`` of ``source``
+        (default: this env; -1 = env e stays as it is) in one launch
+        (mc_sg_copy_envs), ``a_prev`` and its slices of ``planes`` / ``dist``
+        included, so the forked state can be read at once.  Rules as
+        ``BatchCoverageEnv.fork``."""
+        source = self if source is None else source
+        idx = self._fork_index(src_index, source)
+        _lib.check(self.lib.mc_sg_copy_envs(self._h, source._h, idx.data_ptr(), self._stream()),
+                   "mc_sg_copy_envs")
+
+    def sibling(self, num_envs, **overrides):
+        """A new env of ``num_envs`` envs that ``fork`` can copy to and from:
+        the same env_config and grid pool (copied on the device),
+        ``auto_reset`` off unless overridden, reset once."""
+        kw = dict(self._ctor, auto_reset=False)
+        kw.update(overrides)
+        gen = dict(width=self.width, length=self.length, prob_obst=0.0, num_grids=self.num_grids)
+        sib = type(self)(self.config, num_envs, gen=gen, **kw)
+        for f in (_lib.SG_FIELD_GRID_NEG, _lib.SG_FIELD_GRID_POS, _lib.SG_FIELD_NUMPOS):
+            sib.set_state(f, self.get_state(f))
+        sib.reset()
+        return sib
 
     def percent_covered(self):
         """float64 [B]: count_nonzero(_free < 1) / count_nonzero(grid > 0) (:416-421)."""
