@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define MARLCOV_ABI_VERSION 11
+#define MARLCOV_ABI_VERSION 12
 
 enum {
   MC_OK = 0,
@@ -429,6 +429,18 @@ int mc_sg_copy_envs(void* dst, void* src, const int32_t* dev_src, void* stream);
  * 4 = placement failed, 8 = bad injected cell, 16 = motion_penalty KeyError,
  * 32 = mc_sg_copy_envs index. */
 int mc_sg_check(void* env, void* stream);
+/* The kernels mc_sg_step launches for this handle (ABI v12; for tests and
+ * bench lines): the step kernel, for sg_step_rows its lanes per robot
+ * ("rl=4") and "dpp" when it broadcasts by DPP, then the distance kernel:
+ * "sg_step_rows<2,4> rl=4 dpp | sg_erode",
+ * "sg_step_kernel<-1,1> | sg_dist<lds> nt=128" (or sg_dist<global>; nt = its
+ * lanes per workgroup, sg_erode always runs 256).  The string is valid until
+ * the thread's next call; a null env returns "" and sets the error. */
+const char* mc_sg_kernel_variant(void* env);
+/* Name of the index-th step kernel mc_sg_step can select, as
+ * mc_sg_kernel_variant spells it; NULL past the end of the table.  Needs no
+ * device. */
+const char* mc_sg_kernel_name(int32_t index);
 
 /* Diagnostics: in a -DMC_STAMPS build, record per-phase s_memtime stamps of
  * every env into dev_stamps uint64 [B][16]; MC_EINVAL in normal builds. */

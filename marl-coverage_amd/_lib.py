@@ -12,7 +12,7 @@ import re
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libmarlcov.so")
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 MC_OK, MC_EINVAL, MC_EHIP, MC_ESTATE, MC_EDEVICE = 0, -1, -2, -3, -4
 SENSOR_LIDAR, SENSOR_SQUARE = 0, 1
@@ -162,6 +162,8 @@ SIGNATURES = [
     ("mc_sg_set_state", ctypes.c_int, [_VP, _I32, _VP, _I64, _VP]),
     ("mc_sg_copy_envs", ctypes.c_int, [_VP, _VP, _VP, _VP]),
     ("mc_sg_check", ctypes.c_int, [_VP, _VP]),
+    ("mc_sg_kernel_variant", ctypes.c_char_p, [_VP]),
+    ("mc_sg_kernel_name", ctypes.c_char_p, [_I32]),
 ]
 
 _lib = None

@@ -1235,6 +1235,28 @@ int sg_fail(int code, const char* fmt, ...) {
     if (_e != hipSuccess) return sg_fail(MC_EHIP, "%s: %s", #expr, hipGetErrorString(_e)); \
   } while (0)
 
+// Every step kernel mc_sg_step can launch, with the name mc_sg_kernel_variant
+// and mc_sg_kernel_name report for it.
+using SgStepFn = decltype(&mcs::sg_step_kernel<-1, 1>);
+struct SgKernel {
+  const char* name;
+  SgStepFn fn;
+  bool rows;  // sg_step_rows (else sg_step_kernel: one lane per robot)
+  int R;      // compiled radius, -1 = the runtime radius
+  int gpw;    // envs per wave
+};
+#define SG_LANE(R, G) {"sg_step_kernel<" #R "," #G ">", mcs::sg_step_kernel<R, G>, false, R, G}
+#define SG_LANES(R) SG_LANE(R, 1), SG_LANE(R, 2), SG_LANE(R, 4), SG_LANE(R, 8), SG_LANE(R, 16)
+#define SG_ROW(R, G) {"sg_step_rows<" #R "," #G ">", mcs::sg_step_rows<R, G>, true, R, G}
+#define SG_ROWS(R) SG_ROW(R, 1), SG_ROW(R, 2), SG_ROW(R, 4), SG_ROW(R, 8)
+const SgKernel kSgKernels[] = {SG_LANES(-1), SG_LANES(1), SG_LANES(2), SG_LANES(3),
+                               SG_ROWS(1),   SG_ROWS(2),  SG_ROWS(3)};
+#undef SG_LANE
+#undef SG_LANES
+#undef SG_ROW
+#undef SG_ROWS
+constexpr int kNumSgKernels = (int)(sizeof(kSgKernels) / sizeof(kSgKernels[0]));
+
 struct SgEnv {
   mc_sg_config cfg;
   mcs::SState s;
@@ -1248,8 +1270,35 @@ struct SgEnv {
   bool grids_set = false;
   bool stale = true;  // the dist layer does not describe the current maps
   bool rows = true;   // row-parallel step kernel when it applies (MARLCOV_SG_ROWS)
+  int gpw_cap = 4;    // most envs per wave (MARLCOV_SG_GPW)
+  bool force_generic = false;  // MARLCOV_SG_GENERIC=1: A/B against the runtime-radius kernel
+  bool force_sweep = false;    // MARLCOV_SG_SWEEP=1: A/B against the sweep kernel
+  const SgKernel* step = nullptr;  // what mc_sg_step launches (sg_select, at create)
   std::vector<void*> allocs;
 };
+
+// The step kernel of a handle.  Envs per wave: as many groups of (N rounded
+// up to a power of two) lanes as fit 64, capped at 4 (MARLCOV_SG_GPW overrides
+// the cap).  sg_c2 (tools/gpu_sg_gpw.sh, rocprof): 1 17.8 us, 2 14.3, 4 12.8,
+// 8 14.6, 16 19.4 -- past 4 envs per wave there are too few waves to hide the
+// window loads.  Compiled radius and at least 4 lanes per robot: the
+// row-parallel kernel (MARLCOV_SG_ROWS=0 keeps one lane per robot), at most 8
+// envs per wave.
+const SgKernel* sg_select(const SgEnv* E) {
+  const int N = E->s.N, cap = E->gpw_cap;
+  const int R = E->force_generic ? -1 : (E->s.r >= 1 && E->s.r <= 3 ? E->s.r : -1);
+  int p2 = 1;
+  while (p2 < N) p2 *= 2;
+  const bool rows = E->rows && R >= 1 && 4 * p2 <= 64;
+  int gpw = 1;
+  if (rows)
+    while (gpw < 8 && 2 * gpw <= cap && 4 * p2 * 2 * gpw <= 64) gpw *= 2;
+  else
+    while (gpw < 16 && 2 * gpw <= cap && N <= 64 / (2 * gpw)) gpw *= 2;
+  for (const SgKernel& k : kSgKernels)
+    if (k.rows == rows && k.R == R && k.gpw == gpw) return &k;
+  return nullptr;  // (every (rows, R, gpw) the loops above reach is in the table)
+}
 
 SgEnv* as_sg(void* p) { return static_cast<SgEnv*>(p); }
 
@@ -1369,6 +1418,19 @@ int mc_sg_create(const mc_sg_config* cfg, int hip_device, void** out_env) {
     // kernel (read per handle: the parity suite runs both)
     const char* rw = getenv("MARLCOV_SG_ROWS");
     E->rows = !(rw && atoi(rw) == 0);
+    // the A/B knobs of the step and distance kernels, per handle as well
+    const char* gp = getenv("MARLCOV_SG_GPW");
+    E->gpw_cap = gp && atoi(gp) >= 1 ? atoi(gp) : 4;
+    const char* ge = getenv("MARLCOV_SG_GENERIC");
+    E->force_generic = ge && atoi(ge) == 1;
+    const char* sw = getenv("MARLCOV_SG_SWEEP");
+    E->force_sweep = sw && atoi(sw) == 1;
+  }
+  E->step = sg_select(E);
+  if (!E->step) {
+    delete E;
+    return sg_fail(MC_EINVAL, "mc_sg_create: no step kernel for numrobot %d, senseradius %d", c.num_agents,
+                   c.senseradius);
   }
   s.seed = c.seed;
   s.env0 = c.env_offset;
@@ -1379,11 +1441,7 @@ int mc_sg_create(const mc_sg_config* cfg, int hip_device, void** out_env) {
   if (((E->pitch / 2) & 1) == 0) E->pitch += 2;
   E->lds = (size_t)c.width * E->pitch * 2 <= mcs::kLdsLimit;
   E->erode_lds = mcs::erode_lds_bytes(c.width, c.length);
-  static const bool force_sweep = [] {  // MARLCOV_SG_SWEEP=1: A/B against the sweep kernel
-    const char* v = getenv("MARLCOV_SG_SWEEP");
-    return v && atoi(v) == 1;
-  }();
-  E->erode = !force_sweep && c.width + c.length <= 257 && E->erode_lds <= mcs::kLdsLimit;
+  E->erode = !E->force_sweep && c.width + c.length <= 257 && E->erode_lds <= mcs::kLdsLimit;
   const int side = c.width > c.length ? c.width : c.length;
   E->dist_nt = side <= 64 ? 64 : (side <= 128 ? 128 : 256);
   const size_t B = s.B, N = s.N, G = s.G, mw = (size_t)s.W * s.RW;
@@ -1533,69 +1591,42 @@ int mc_sg_step(void* env, const uint8_t* dev_actions, const int32_t* dev_quot, d
   hipStream_t st = (hipStream_t)stream;
   SG_TRY(hipSetDevice(E->device));
   if (E->stale) SG_TRY(launch_dist(E, st));  // the pre-move distance_map of the current maps
-  // envs per wave: as many groups of (N rounded up to a power of two) lanes
-  // as fit 64, capped at 4 (MARLCOV_SG_GPW overrides the cap).  sg_c2
-  // (tools/gpu_sg_gpw.sh, rocprof): 1 17.8 us, 2 14.3, 4 12.8, 8 14.6, 16 19.4
-  // -- past 4 envs per wave there are too few waves to hide the window loads
-  static const int gpw_cap = [] {
-    const char* v = getenv("MARLCOV_SG_GPW");
-    const int c = v ? atoi(v) : 4;
-    return c >= 1 ? c : 4;
-  }();
-  int gpw = 1;
-  while (gpw < 16 && 2 * gpw <= gpw_cap && E->s.N <= 64 / (2 * gpw)) gpw *= 2;
-  static const bool force_generic = [] {  // MARLCOV_SG_GENERIC=1: A/B against the runtime-radius kernel
-    const char* v = getenv("MARLCOV_SG_GENERIC");
-    return v && atoi(v) == 1;
-  }();
-  const int R = force_generic ? -1 : (E->s.r >= 1 && E->s.r <= 3 ? E->s.r : -1);
-  decltype(&mcs::sg_step_kernel<-1, 1>) kern = nullptr;
-  // compiled radius and at least 4 lanes per robot: the row-parallel kernel
-  // (MARLCOV_SG_ROWS=0 at create keeps one lane per robot)
-  int p2 = 1;
-  while (p2 < E->s.N) p2 *= 2;
-  if (E->rows && R >= 1 && 4 * p2 <= 64) {
-    gpw = 1;
-    while (2 * gpw <= gpw_cap && 4 * p2 * 2 * gpw <= 64) gpw *= 2;
-#define SG_PICK_ROWS(RR)                                             \
-  switch (gpw) {                                                     \
-    case 1: kern = mcs::sg_step_rows<RR, 1>; break;                  \
-    case 2: kern = mcs::sg_step_rows<RR, 2>; break;                  \
-    case 4: kern = mcs::sg_step_rows<RR, 4>; break;                  \
-    default: kern = mcs::sg_step_rows<RR, 8>; break;                 \
-  }
-    switch (R) {
-      case 1: SG_PICK_ROWS(1); break;
-      case 2: SG_PICK_ROWS(2); break;
-      default: SG_PICK_ROWS(3); break;
-    }
-#undef SG_PICK_ROWS
-  }
-#define SG_PICK(RR)                                                  \
-  switch (gpw) {                                                     \
-    case 1: kern = mcs::sg_step_kernel<RR, 1>; break;                \
-    case 2: kern = mcs::sg_step_kernel<RR, 2>; break;                \
-    case 4: kern = mcs::sg_step_kernel<RR, 4>; break;                \
-    case 8: kern = mcs::sg_step_kernel<RR, 8>; break;                \
-    default: kern = mcs::sg_step_kernel<RR, 16>; break;              \
-  }
-  if (kern == nullptr) {
-    switch (R) {  // compile-time radii of the reference configs (staged window)
-      case 1: SG_PICK(1); break;
-      case 2: SG_PICK(2); break;
-      case 3: SG_PICK(3); break;
-      default: SG_PICK(-1); break;
-    }
-  }
-#undef SG_PICK
-  const int per_block = mcs::kEnvsPerBlock * gpw;
+  const SgKernel& k = *E->step;
+  const int per_block = mcs::kEnvsPerBlock * k.gpw;
   const int blocks = (E->s.B + per_block - 1) / per_block;
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * mcs::kEnvsPerBlock), 0, st, E->s, dev_actions, dev_quot,
+  hipLaunchKernelGGL(k.fn, dim3(blocks), dim3(64 * mcs::kEnvsPerBlock), 0, st, E->s, dev_actions, dev_quot,
                      dev_reward, dev_done);
   SG_TRY(hipGetLastError());
   SG_TRY(launch_dist(E, st));
   E->stale = false;
   return MC_OK;
+}
+
+const char* mc_sg_kernel_variant(void* env) {
+  SgEnv* E = as_sg(env);
+  if (!E) {
+    sg_fail(MC_EINVAL, "mc_sg_kernel_variant: null env");
+    return "";
+  }
+  thread_local std::string name;
+  const SgKernel& k = *E->step;
+  name = k.name;
+  if (k.rows) {  // lanes per robot, and the DPP broadcasts (sg_step_rows: RL, dpp)
+    int p2 = 1;
+    while (p2 < E->s.N) p2 *= 2;
+    const int NG = 64 / k.gpw, RL = NG / p2;
+    name += " rl=" + std::to_string(RL);
+    if (NG == 16 && RL == 4 && !E->s.scan) name += " dpp";
+  }
+  if (E->erode)
+    name += " | sg_erode";
+  else
+    name += std::string(" | sg_dist<") + (E->lds ? "lds" : "global") + "> nt=" + std::to_string(E->dist_nt);
+  return name.c_str();
+}
+
+const char* mc_sg_kernel_name(int32_t index) {
+  return index >= 0 && index < kNumSgKernels ? kSgKernels[index].name : nullptr;
 }
 
 int64_t mc_sg_field_bytes(void* env, int32_t f) {

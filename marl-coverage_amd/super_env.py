@@ -258,6 +258,10 @@ class BatchSuperGridEnv:
         eg = self.get_state(_lib.SG_FIELD_ENV_GRID).long()
         return cc / npos[eg]
 
+    def kernel_variant(self) -> str:
+        """The step and distance kernels mc_sg_step launches (mc_sg_kernel_variant)."""
+        return self.lib.mc_sg_kernel_variant(self._h).decode()
+
     def check(self):
         _lib.check(self.lib.mc_sg_check(self._h, self._stream()), "mc_sg_check")
 

@@ -31,7 +31,7 @@ def test_copy_envs_signatures_and_abi(lib):
         assert name in typed
         res, args = typed[name]
         assert len(args) == 4  # dst, src, dev_src, stream
-    assert _lib.ABI_VERSION == 11 == lib.mc_abi_version()
+    assert _lib.ABI_VERSION == 12 == lib.mc_abi_version()  # v11 added the calls, v12 mc_sg_kernel_variant
     assert _lib.ERR_FORK == 1 << 5
 
 

@@ -90,6 +90,27 @@ def test_create_rejects_bad_config(lib, bad, msg):
     assert msg in lib.mc_last_error().decode()
 
 
+@pytest.mark.parametrize("n,beams,rng,msg", [
+    (21, 13, 27.0, "64 KiB"),        # 8 x 8 window tiles: 21 robots need 66,512 B of LDS
+    (33, 13, 27.0, "window tiles"),  # 33 x 64 = 2,112 staged tiles > 2,048
+    (20, 13, 27.0, None),            # the largest accepted slot (63,376 B; tests/test_gpu_launch_shapes.py)
+    (32, 1, 27.0, "64 KiB"),         # 2,048 tiles pass the tile limit; the LDS limit refuses them
+])
+def test_create_window_limits(lib, n, beams, rng, msg):
+    """numrobot x TW^2 <= 2,048 staged tiles and <= 64 KiB of
+    LDS per env, both checked before the first HIP call."""
+    from marlcov import _lib
+    h = ctypes.c_void_p()
+    rc = lib.mc_create(ctypes.byref(_cfg(num_agents=n, num_beams=beams, lidar_range=rng)), 0, ctypes.byref(h))
+    if msg is None:  # accepted: created, or (no device here) stopped by the HIP runtime, not by a limit
+        assert rc in (_lib.MC_OK, _lib.MC_EHIP), lib.mc_last_error().decode()
+        if h.value:
+            lib.mc_destroy(h)
+        return
+    assert rc == _lib.MC_EINVAL and not h.value
+    assert msg in lib.mc_last_error().decode()
+
+
 def test_null_arguments_are_errors(lib):
     assert lib.mc_create(None, 0, None) == -1
     assert lib.mc_step(None, None, None, None, None, None, None) == -1
@@ -382,6 +403,34 @@ def test_kernel_variant_null_env(lib):
     assert lib.mc_kernel_variant(None) == b""
     assert "null" in lib.mc_last_error().decode()
     assert lib.mc_random_actions(None, 0, 0, None, None) == -1
+
+
+def test_super_kernel_variant_null_env(lib):
+    assert lib.mc_sg_kernel_variant(None) == b""
+    msg = lib.mc_last_error().decode()
+    assert "mc_sg_kernel_variant" in msg and "null" in msg, msg
+
+
+def test_super_dispatch_table_is_covered(lib):
+    """Every step kernel mc_sg_step can select (mc_sg_kernel_name walks the
+    dispatcher's own table) is named by a parametrized case of
+    tests/test_gpu_super.py, which asserts it through kernel_variant and runs
+    it against the oracle: a new instantiation needs a case before this
+    passes.  The table holds at least sg_step_kernel<R, 1..16> and
+    sg_step_rows<R, 1..8> for the runtime radius (-1, sg_step_kernel only) and
+    the compiled radii 1..3."""
+    import test_gpu_super
+    table = []
+    while (name := lib.mc_sg_kernel_name(len(table))) is not None:
+        table.append(name.decode())
+    assert lib.mc_sg_kernel_name(-1) is None
+    assert len(set(table)) == len(table)
+    known = {f"sg_step_kernel<{r},{g}>" for r in (-1, 1, 2, 3) for g in (1, 2, 4, 8, 16)}
+    known |= {f"sg_step_rows<{r},{g}>" for r in (1, 2, 3) for g in (1, 2, 4, 8)}
+    assert known <= set(table), sorted(known - set(table))
+    declared = test_gpu_super.declared_step_kernels()
+    assert set(table) <= declared, sorted(set(table) - declared)
+    assert declared <= set(table), sorted(declared - set(table))  # no case expects a kernel that does not exist
 
 
 def test_gridload_reference_png_maps(tmp_path):
