@@ -16,6 +16,7 @@
 #include "marlcov.h"
 #include "mc_internal.h"
 #include "mc_fork.h"
+#include "mc_vistab.h"
 
 namespace mc {
 hipError_t launch_env(const State& s, int mode, const uint8_t* actions, const uint8_t* env_mask,
@@ -28,6 +29,7 @@ hipError_t launch_pack(const State& s, const int8_t* grids, hipStream_t stream);
 hipError_t launch_gen(const State& s, uint64_t seed, double p, hipStream_t stream);
 hipError_t launch_random_actions(const State& s, uint64_t seed, int step, uint8_t* out, hipStream_t stream);
 const char* env_variant(const State& s, int nt, int epw);
+bool env_takes_vis_table(const State& s, int nt, int epw);
 hipError_t launch_dijkstra(const State& s, int pad, int layer, int Lc, uint8_t* obs,
                            uint32_t* list, bool window, uint64_t* big, unsigned big_slots,
                            hipStream_t stream);
@@ -95,6 +97,11 @@ struct Env {
   size_t fan_cap = 0;         // words allocated in fan_buf
   void* rayprog_buf = nullptr;  // u32: the ray programs (State::ray_prog; common beam patterns)
   size_t rayprog_cap = 0;       // words allocated in rayprog_buf
+  // the lidar's visibility table (State::vis_tab; mc_vistab.h): MARLCOV_VIS_TABLE
+  // 0 off / 1 on (default) / 2 require, and MARLCOV_VIS_TABLE_MB, read at mc_create
+  int vis_mode = 1;
+  size_t vis_cap = 0;       // largest table to build, bytes
+  void* vis_buf = nullptr;  // G x Wp x Lp records (allocated at the first build)
   int beam_count = 0;
   bool grids_set = false;
   std::vector<void*> allocs;
@@ -171,6 +178,36 @@ int env_threads(const mc::State& s) {
 }
 
 Env* as_env(void* p) { return static_cast<Env*>(p); }
+
+int launch_epw(const Env* E);
+
+// (Re)build the visibility table on `st` after the pool or the beam table
+// changed -- once both are there -- or drop it when this state's step kernel
+// would not read one (no ray programs, another shape), the pool's table
+// exceeds MARLCOV_VIS_TABLE_MB or its allocation fails: the step then marches,
+// unless MARLCOV_VIS_TABLE=require asks for an error instead.
+int vis_refresh(Env* E, hipStream_t st, const char* who) {
+  mc::State& s = E->s;
+  s.vis_tab = nullptr;
+  if (E->vis_mode == 0 || !E->beams_set || !E->grids_set) return MC_OK;
+  const uint64_t cells = (uint64_t)s.G * s.Wp * s.Lp;
+  const uint64_t bytes = cells * mc::kVisRecWords * 4;
+  char why[160] = "";
+  if (s.sensor != MC_SENSOR_LIDAR || !mc::vis_fits(s.H) || !mc::env_takes_vis_table(s, E->nt, launch_epw(E)))
+    snprintf(why, sizeof(why), "no step kernel of this shape and beam table reads a visibility table");
+  else if (cells >= (1ull << 31) || bytes > E->vis_cap)
+    snprintf(why, sizeof(why), "the pool's table of %llu MB exceeds MARLCOV_VIS_TABLE_MB = %llu",
+             (unsigned long long)(bytes >> 20), (unsigned long long)(E->vis_cap >> 20));
+  else if (!E->vis_buf && hipMalloc(&E->vis_buf, (size_t)bytes) != hipSuccess) {
+    (void)hipGetLastError();  // (cleared: the fallback is not an error)
+    E->vis_buf = nullptr;
+    snprintf(why, sizeof(why), "allocating the table's %llu MB failed", (unsigned long long)(bytes >> 20));
+  }
+  if (why[0]) return E->vis_mode == 2 ? fail(MC_EINVAL, "%s: MARLCOV_VIS_TABLE=require, but %s", who, why) : MC_OK;
+  HIP_TRY(mc::launch_vis_build(s, (uint32_t*)E->vis_buf, st));
+  s.vis_tab = (const uint32_t*)E->vis_buf;
+  return MC_OK;
+}
 
 // lanes per env workgroup and envs per workgroup for the current state
 // (mc_create, and again when mc_set_beam_table changes the beam count)
@@ -281,8 +318,20 @@ int mc_create(const mc_config* cfg, int hip_device, void** out_env) {
                         TW <= 4 ? 4 : 8) > 65536)
     return fail(MC_EINVAL, "per-env LDS window exceeds 64 KiB (numrobot / range / num_lasers too large)");
 
+  // the visibility table's switches, per handle (not cached: tests set them per env)
+  int vis_mode = 1;
+  size_t vis_cap = (size_t)16384 << 20;
+  if (const char* v = getenv("MARLCOV_VIS_TABLE")) vis_mode = v[0] == '0' ? 0 : (strcmp(v, "require") == 0 ? 2 : 1);
+  if (const char* v = getenv("MARLCOV_VIS_TABLE_MB")) vis_cap = (size_t)strtoull(v, nullptr, 10) << 20;
+  if (vis_mode == 2 && (c.sensor_type != MC_SENSOR_LIDAR || !mc::vis_fits(H)))
+    return fail(MC_EINVAL, "mc_create: MARLCOV_VIS_TABLE=require, but a visibility record holds a lidar of "
+                "half-width <= %d only (this env: %s, H = %d)", (mc::kVisRows - 1) / 2,
+                c.sensor_type == MC_SENSOR_LIDAR ? "lidar" : "square sensor", H);
+
   Env* E = new Env();
   E->cfg = c;
+  E->vis_mode = vis_mode;
+  E->vis_cap = vis_cap;
   E->range = c.lidar_range;
   E->device = hip_device;
   mc::State& s = E->s;
@@ -530,6 +579,7 @@ void mc_destroy(void* env) {
   if (E->bits_buf) (void)hipFree(E->bits_buf);
   if (E->fan_buf) (void)hipFree(E->fan_buf);
   if (E->rayprog_buf) (void)hipFree(E->rayprog_buf);
+  if (E->vis_buf) (void)hipFree(E->vis_buf);
   delete E;
 }
 
@@ -780,6 +830,7 @@ int mc_set_beam_table(void* env, const double* host_table, int32_t num_beams) {
   E->s.fan_nsec = E->s.fan_nspec = E->s.fan_kt = E->s.fan_words = 0;
   E->s.fan_data = nullptr;
   E->s.ray_prog = nullptr;
+  E->s.vis_tab = nullptr;
   if (num_beams != E->beam_count || !E->beams_buf) {
     // the reference lets callers swap _thetalist after construction
     // (even beam counts): (re-)size the device tables
@@ -863,6 +914,10 @@ int mc_set_beam_table(void* env, const double* host_table, int32_t num_beams) {
     }
   }
   E->beams_set = true;
+  // the visibility table of the new beams (the null stream; done before the
+  // call returns, as the tables above are)
+  if (int rc = vis_refresh(E, nullptr, "mc_set_beam_table"); rc != MC_OK) return rc;
+  HIP_TRY(hipDeviceSynchronize());
   return MC_OK;
 }
 
@@ -889,7 +944,9 @@ int mc_set_grids(void* env, const int8_t* dev_grids, int32_t num_grids, void* st
   HIP_TRY(hipSetDevice(E->device));
   HIP_TRY(hipMemsetAsync((void*)E->s.numfree, 0, (size_t)E->s.G * 4, st));
   HIP_TRY(mc::launch_pack(E->s, dev_grids, st));
-  return check_numfree(E, st);
+  E->s.vis_tab = nullptr;  // the old pool's table is never read again
+  if (int rc = check_numfree(E, st); rc != MC_OK) return rc;
+  return vis_refresh(E, st, "mc_set_grids");
 }
 
 int mc_generate_grids(void* env, uint64_t seed, double p_obst, void* stream) {
@@ -900,7 +957,9 @@ int mc_generate_grids(void* env, uint64_t seed, double p_obst, void* stream) {
   HIP_TRY(hipSetDevice(E->device));
   HIP_TRY(hipMemsetAsync((void*)E->s.numfree, 0, (size_t)E->s.G * 4, st));
   HIP_TRY(mc::launch_gen(E->s, seed, p_obst, st));
-  return check_numfree(E, st);
+  E->s.vis_tab = nullptr;
+  if (int rc = check_numfree(E, st); rc != MC_OK) return rc;
+  return vis_refresh(E, st, "mc_generate_grids");
 }
 
 int mc_random_actions(void* env, uint64_t seed, int32_t step, uint8_t* dev_actions, void* stream) {
@@ -1085,6 +1144,8 @@ int mc_set_state(void* env, int32_t f, const void* dev_src, int64_t bytes, void*
   HIP_TRY(hipSetDevice(E->device));
   if (int rc = copy_field(E, d, const_cast<void*>(dev_src), /*to_env=*/true, (hipStream_t)stream); rc != MC_OK) return rc;
   if (f == MC_FIELD_GRID_NEG || f == MC_FIELD_GRID_POS || f == MC_FIELD_NUMFREE) E->grids_set = true;
+  if (f == MC_FIELD_GRID_NEG)  // an uploaded pool (a sibling's copy): its own visibility table
+    if (int rc = vis_refresh(E, (hipStream_t)stream, "mc_set_state"); rc != MC_OK) return rc;
   E->dist_pre_stale = true;  // uploaded maps / positions: recompute the PRE terms
   if (E->s.dist_mw)  // and max(d) of every map
     HIP_TRY(hipMemsetAsync(E->s.dist_mw, 0xFF, (size_t)E->s.B * E->s.N * 8, (hipStream_t)stream));

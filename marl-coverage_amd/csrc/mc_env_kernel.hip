@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "mc_device.h"
+#include "mc_vistab.h"
 
 namespace mc {
 
@@ -229,7 +230,12 @@ struct Ctx {
                                   sizeof(WT) == 4 && SH::N * SH::NB <= RPL * LPE;
   static constexpr int RPW = RAYPROG ? ray_prog_row_words(RPL, SH::KM) : 4;  // words of a lane's program row
   static_assert(!RAYPROG || ray_prog_span(SH::N, (int)sizeof(WT), SH::KM) <= 32767, "ray program offsets are int16");
-  uint32_t rp[RPW];  // RAYPROG: this lane's program row (round trip 1)
+  // a step's lidar marks from the visibility table (mc_vistab.h; select_env:
+  // State::vis_tab is set) instead of the march: 8 lanes per agent land one
+  // record.  Only a reset's initial sense still marches (from its own program
+  // row, reset_env)
+  static constexpr bool VISTAB = RAYPROG && SH::VT != 0 && vis_fits(SH::H) && 8 * SH::N <= LPE;
+  uint32_t rp[RPW];  // RAYPROG: this lane's program row (round trip 1; VISTAB: a reset's only)
   int sub;    // lane within the env
   int lane0;  // first lane of this env's slot within the wave
   int e;      // env index
@@ -477,8 +483,10 @@ __device__ __forceinline__ uint64_t transpose8(uint64_t x) {
 }
 
 // round trip 2, landing: the grid tiles into the row planes (and the tile
-// planes for the square sensor; the column planes for the fan march)
-template <class CT, typename WT = typename CT::WT>
+// planes for the square sensor; the column planes for the fan march).
+// NEGR false: no grid row plane (a step whose marks come from the visibility
+// table: nothing reads it); the tiles outside the map still become obstacles
+template <class CT, bool NEGR = true, typename WT = typename CT::WT>
 __device__ __forceinline__ void stage_scatter(const State& s, const CT& C, Items<CT::KI>& I) {
   constexpr int LPE = CT::LPE, KI = CT::KI;
   [[maybe_unused]] constexpr int EPW = CT::EPW;  // STAMP
@@ -509,8 +517,10 @@ __device__ __forceinline__ void stage_scatter(const State& s, const CT& C, Items
       const size_t off = (size_t)row_word<WT>(s, I.a[k], 8 * I.ti[k]) * sizeof(WT) + I.tj[k];
       const size_t rs = (size_t)row_step<WT>(s) * sizeof(WT);  // one window row
       const uint64_t ft = (known && I.masks && in) ? (I.f[k] | I.o[k]) : 0ull;
+      if constexpr (NEGR) {
 #pragma unroll
-      for (int r = 0; r < 8; ++r) nb[off + r * rs] = (uint8_t)(nt >> (8 * r));
+        for (int r = 0; r < 8; ++r) nb[off + r * rs] = (uint8_t)(nt >> (8 * r));
+      }
       if (known) {  // the cells the agent has seen (old free | obstacle tiles), the same way
 #pragma unroll
         for (int r = 0; r < 8; ++r) fb[off + r * rs] = (uint8_t)(ft >> (8 * r));
@@ -775,10 +785,12 @@ __device__ __forceinline__ uint32_t ray_p0(const State& s, const Lds<WT>& L, int
 // Moves from registers (Front): robot i's target-cell bit (grid < 0 or out of
 // bounds) was loaded by lane lane0 + i next to round trip 2 and is shared by
 // a ballot; every lane of the slot replays the robot-order loop; lane 0
-// publishes the result.  Same semantics as moves_regs.
+// publishes the result.  Same semantics as moves_regs.  xy_after (VISTAB):
+// every robot's post-move cell, packed like Front::xy, for every lane.
 template <class CT, int NS>
 __device__ __forceinline__ void moves_front(const State& s, const CT& C, const Front<NS>& F, bool tgt_blk,
-                                            uint32_t txy, int act_own, uint64_t moved, double pen_unit) {
+                                            uint32_t txy, int act_own, uint64_t moved, double pen_unit,
+                                            uint32_t* xy_after = nullptr) {
   const Lds<typename CT::WT>& L = C.L;
   // QUAD: every lane holds its quad's robot (sub % NS): its packed target
   // and flags (bit 0 blocked, bit 1 acts) go to the loop by quad_perm
@@ -815,16 +827,116 @@ __device__ __forceinline__ void moves_front(const State& s, const CT& C, const F
     }
     if (acts && !ok) pen += pen_unit;  // reward += -collision_penalty (:203)
   }
+  if (xy_after != nullptr) {
+#pragma unroll
+    for (int i = 0; i < NS; ++i) xy_after[i] = XY[i];
+  }
   if (C.sub == 0) {
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
       L.x[i] = (int)(XY[i] & 0xFFFFu);
       L.y[i] = (int)(XY[i] >> 16);
-      if constexpr (CT::RAYPROG)
+      if constexpr (CT::RAYPROG && !CT::VISTAB)  // (VISTAB: no march in a step)
         ray_p0_words(L)[i] = ray_p0(s, L, i, (int)(XY[i] & 0xFFFFu), (int)(XY[i] >> 16), F.bx[i], F.by[i]);
     }
     L.sc->pen = pen;
     L.sc->moved = moved;
+  }
+}
+
+// --------------------------------------------------------------------------
+// Visibility table (Ctx::VISTAB; mc_vistab.h): a step's lidar marks are the
+// record of the robot's post-move cell.  After the moves, lanes 8a .. 8a + 7
+// of the slot load 16 bytes each of the record of robot a's cell (vis_load)
+// and shift its rows into the mark-row plane (vis_land) -- where the march
+// would have left the same bits.  (MC_VIS_LATE 0, an A/B knob: a robot ends
+// its move on its own cell or on its target cell, both known after round trip
+// 1, so both records are loaded next to round trip 2 and one is selected
+// after the moves.)  Rows 4c .. 4c + 3 belong to lane 8a + c; a record has
+// 2H + 1 rows, so the lanes past the last row's quad reread that quad and
+// store nothing, like the lanes past 8N of a one-env workgroup.
+// --------------------------------------------------------------------------
+template <int NS>
+struct VisRec {
+  int4 own, tgt;  // this lane's quad of the records of the pre-move cell and of the target cell
+  uint32_t xy0;   // the pre-move cell of the lane's robot (Front::xy)
+};
+
+// pick() for the packed cells
+template <int NS>
+__device__ __forceinline__ uint32_t pick_u(const uint32_t (&v)[NS], int a) {
+  uint32_t r = v[0];
+#pragma unroll
+  for (int i = 1; i < NS; ++i) {
+    r = a == i ? v[i] : r;
+    asm volatile("" : "+v"(r));  // (as in pick: keeps the chain from becoming an indexed scratch array)
+  }
+  return r;
+}
+
+// MC_VIS_LATE 1 (default): one record load after the moves -- a dependent
+// round trip, but half the table traffic.  0 (A/B knob): both candidates'
+// records loaded next to round trip 2 and selected after the moves.  Measured
+// (profiles/r11/vistab/): 6.48-6.78 against 6.75-6.95 us at K = 200 and
+// 7.20-7.61 against 7.08-8.25 us at K = 20; the parent 7.73-7.76 / 8.12-8.39.
+#ifndef MC_VIS_LATE
+#define MC_VIS_LATE 1
+#endif
+
+// xy_after (MC_VIS_LATE): the robots' post-move cells -- that one record only
+template <class CT, int NS>
+__device__ __forceinline__ VisRec<NS> vis_load(const State& s, const CT& C, int g, const Front<NS>& F,
+                                               const uint32_t* xy_after = nullptr) {
+  constexpr int QL = (2 * CT::SH::H) / 4;  // the quad of the last row
+  const int av = min(C.sub >> 3, NS - 1), ch = min(C.sub & 7, QL);
+  VisRec<NS> V;
+  V.xy0 = pick_u<NS>(F.xy, av);
+  if (xy_after != nullptr) {
+    uint32_t xa[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) xa[i] = xy_after[i];
+    V.xy0 = pick_u<NS>(xa, av);
+    const uint32_t last = (uint32_t)s.G * (uint32_t)s.Wp * (uint32_t)s.Lp - 1u;
+    const uint32_t i0 = min(vis_index(s.Wp, s.Lp, g, (int)(V.xy0 & 0xFFFFu), (int)(V.xy0 >> 16)), last);
+    V.own = V.tgt = *reinterpret_cast<const int4*>(reinterpret_cast<const char*>(s.vis_tab) + ch * 16 +
+                                                   (size_t)i0 * (kVisRecWords * 4));
+    return V;
+  }
+  const int act = pick<NS>(F.act, av);
+  const int x = (int)(V.xy0 & 0xFFFFu), y = (int)(V.xy0 >> 16);
+  const int tx = x + (act == 0) - (act == 2), ty = y + (act == 1) - (act == 3);
+  const bool inb = (unsigned)tx < (unsigned)s.Wp && (unsigned)ty < (unsigned)s.Lp;  // (else: blocked, the own cell again)
+  // never past the table, whatever the positions hold
+  const uint32_t last = (uint32_t)s.G * (uint32_t)s.Wp * (uint32_t)s.Lp - 1u;
+  const uint32_t i0 = min(vis_index(s.Wp, s.Lp, g, x, y), last);
+  const uint32_t i1 = min(vis_index(s.Wp, s.Lp, g, inb ? tx : x, inb ? ty : y), last);
+  const char* tab = reinterpret_cast<const char*>(s.vis_tab) + ch * 16;
+  V.own = *reinterpret_cast<const int4*>(tab + (size_t)i0 * (kVisRecWords * 4));
+  V.tgt = *reinterpret_cast<const int4*>(tab + (size_t)i1 * (kVisRecWords * 4));
+  return V;
+}
+
+// xy_after: every robot's post-move cell (moves_front)
+template <class CT, int NS, typename WT = typename CT::WT>
+__device__ __forceinline__ void vis_land(const State& s, const CT& C, const Front<NS>& F, const VisRec<NS>& V,
+                                         const uint32_t (&xy_after)[NS]) {
+  static_assert(sizeof(WT) == 4, "a record row lands in a 32-bit window row");
+  constexpr int H = CT::SH::H, QL = (2 * H) / 4;
+  const int av = min(C.sub >> 3, NS - 1), ch = C.sub & 7;
+  const uint32_t xy = pick_u<NS>(xy_after, av);
+  const int4 r = xy == V.xy0 ? V.own : V.tgt;
+  // the record's row 0 / bit 0 in the agent's block: x - H - 8 bx in 0 .. 9,
+  // y - H - 8 by likewise (the block starts at most 7 cells before x0 - H - 1
+  // and the robot moved at most one cell): 21 + 9 bits fit the row
+  const int lx = (int)(xy & 0xFFFFu) - H - 8 * pick<NS>(F.bx, av) + 4 * ch;
+  const int sh = (int)(xy >> 16) - H - 8 * pick<NS>(F.by, av);
+  if (C.sub < 8 * NS && ch <= QL) {
+    WT* row = C.L.fpr + row_word<WT>(s, av, lx);
+    const int rs = row_step<WT>(s);
+    const uint32_t w[4] = {(uint32_t)r.x, (uint32_t)r.y, (uint32_t)r.z, (uint32_t)r.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (ch < QL || 4 * QL + j <= 2 * H) row[j * rs] = w[j] << sh;  // (the last quad: rows up to 2H only)
   }
 }
 
@@ -1695,12 +1807,15 @@ __device__ __forceinline__ void sentinel_done(const State& s, const EnvIO& io, i
   s.ep_len[e] = cs;
 }
 
-// sense -> (lidar: gather) -> (single tool) -> merge, with the barriers
-template <class CT>
+// sense -> (lidar: gather) -> (single tool) -> merge, with the barriers.
+// MARKED: the mark rows are written already (vis_land): no march
+template <class CT, bool MARKED = false>
 __device__ __forceinline__ void sense_and_merge(const State& s0, const CT& C, Items<CT::KI>& I) {
   [[maybe_unused]] constexpr int EPW = CT::EPW;  // STAMP
   State s = s0;
-  if (MC_ABL != 5) sense(s, C);
+  if constexpr (!MARKED) {
+    if (MC_ABL != 5) sense(s, C);
+  }
   __syncthreads();
   STAMP(13);
   if (s.sensor == 0) {
@@ -2115,7 +2230,8 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
   const bool lidar = s.sensor == 0;
   const int nbl = lidar ? s.nbeams : 1;  // a square env reads a dummy record
   // (RAYPROG: the lane's ray program row instead of a beam record)
-  if constexpr (CT::RAYPROG) load_ray_prog(s, C);
+  // (VISTAB: a step does not march; reset_env loads the row for itself)
+  if constexpr (CT::RAYPROG && !CT::VISTAB) load_ray_prog(s, C);
   const int4 bm0 = CT::RAYPROG ? make_int4(0, 0, 0, 0)
                                : reinterpret_cast<const int4*>(lidar ? (const void*)s.beams : (const void*)s.pos)
                                      [C.sub < nbl ? C.sub : 0];
@@ -2144,7 +2260,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
   // the branch that uses it (that would make it a round trip of its own)
   asm volatile("" ::"v"(p0.x), "v"(p0.y), "v"(act_raw), "v"(act0_raw), "v"(req_raw), "v"(g0),
                "v"(bm0.x), "v"(bm0.w), "v"(mwv.x), "v"(mwv.y), "v"(chd.x), "v"(chd.w), "v"(chb.y));
-  if constexpr (CT::RAYPROG) {
+  if constexpr (CT::RAYPROG && !CT::VISTAB) {
 #pragma unroll
     for (int q = 0; q < CT::RPW; q += 4) asm volatile("" ::"v"(C.rp[q]));
   }
@@ -2213,10 +2329,25 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
       const bool inb = (unsigned)tx < (unsigned)s.Wp && (unsigned)ty < (unsigned)s.Lp;
       const uint64_t tt = ld_tile<O32>(s.grid_neg, __umul24((uint32_t)g0, (uint32_t)s.MT) +
                                                        tile_index24(s.TCS, inb ? tx >> 3 : 0, inb ? ty >> 3 : 0));
-      stage_load(s, C, g0, true, I, &F);
-      moves_front(s, C, F, !inb || ((tt >> tile_bit(tx, ty)) & 1ull), (uint32_t)tx | ((uint32_t)ty << 16), act,
-                  moved0, -s.pen);
-      stage_scatter(s, C, I);
+      if constexpr (CT::VISTAB) {
+        // ... and both candidate records of every robot, before the staged
+        // tiles (loads return in order: the mask tiles stay in flight past
+        // the landing)
+        VisRec<NSM> V;
+        if constexpr (!MC_VIS_LATE) V = vis_load(s, C, g0, F);
+        stage_load(s, C, g0, true, I, &F);
+        uint32_t xy_after[NSM];
+        moves_front(s, C, F, !inb || ((tt >> tile_bit(tx, ty)) & 1ull), (uint32_t)tx | ((uint32_t)ty << 16), act,
+                    moved0, -s.pen, xy_after);
+        if constexpr (MC_VIS_LATE) V = vis_load(s, C, g0, F, xy_after);
+        vis_land(s, C, F, V, xy_after);
+        stage_scatter<CT, false>(s, C, I);
+      } else {
+        stage_load(s, C, g0, true, I, &F);
+        moves_front(s, C, F, !inb || ((tt >> tile_bit(tx, ty)) & 1ull), (uint32_t)tx | ((uint32_t)ty << 16), act,
+                    moved0, -s.pen);
+        stage_scatter(s, C, I);
+      }
     } else if constexpr (EARLY) {
       // ---- round trip 2 with the moves of a multi-wave env: the first wave
       // moves the robots from registers (front_regs / moves_front: lane i
@@ -2289,7 +2420,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
       dpre0 = pr[0];
       dprek = pr[1 + k];
     }
-    sense_and_merge(s, C, I);
+    sense_and_merge<CT, CT::VISTAB>(s, C, I);
     __syncthreads();
     STAMP(5);
     reload_state<SH, EPW>(s, io);
@@ -2538,6 +2669,10 @@ using ShapeC4B = Shape<8, 20, 360, 2, 20, 15, 3, 0, 64, 2, 2384, 258>;
 using ShapeC2B = Shape<4, 10, 21, 2, 10, 8, 3, 0, 0, 0, 0, 130>;
 using ShapeC5B = Shape<16, 10, 21, 2, 10, 8, 4, 1, 0, 0, 0, 514>;
 using ShapeC5 = Shape<16, 10, 21, 2, 10, 8, 4, 1>;  // 16 agents, egoradius 2, dist_reward (4 obs layers)
+// the C2 shapes with the lidar's marks read from the visibility table (Ctx::VISTAB)
+using ShapeC2V = Shape<4, 10, 21, 2, 10, 8, 3, 0, 0, 0, 0, 0, 1>;
+using ShapeC2DV = Shape<4, 10, 21, 2, 10, 8, 4, 0, 0, 0, 0, 0, 1>;
+using ShapeC2BV = Shape<4, 10, 21, 2, 10, 8, 3, 0, 0, 0, 0, 130, 1>;
 
 
 #define MC_EL(T, P, W, SH, NAME) \
@@ -2570,7 +2705,13 @@ EnvLaunch select_env(const State& s, int nt, int epw) {
   // (Ctx::RAYPROG): without one (beam patterns that depend on the start, or
   // MARLCOV_BEAM_TABLE) the generic kernel of the same geometry runs
   const bool rp = s.ray_prog != nullptr;
+  // ... and read a step's marks from the visibility table when the handle has
+  // one (mc_capi.hip vis_refresh); the same names: the table is not a shape
+  const bool vt = rp && s.vis_tab != nullptr;
   if (epw == 2) {
+    if (narrow && fits32 && spec && vt && ShapeC2BV::matches(s)) return MC_EL(64, 2, uint32_t, ShapeC2BV, "u32,C2");
+    if (narrow && fits32 && spec && vt && ShapeC2V::matches(s)) return MC_EL(64, 2, uint32_t, ShapeC2V, "u32,C2");
+    if (narrow && fits32 && spec && vt && ShapeC2DV::matches(s)) return MC_EL(64, 2, uint32_t, ShapeC2DV, "u32,C2D");
     if (narrow && fits32 && spec && rp && ShapeC2B::matches(s)) return MC_EL(64, 2, uint32_t, ShapeC2B, "u32,C2");
     if (narrow && fits32 && spec && rp && ShapeC2::matches(s)) return MC_EL(64, 2, uint32_t, ShapeC2, "u32,C2");
     if (narrow && fits32 && spec && rp && ShapeC2D::matches(s)) return MC_EL(64, 2, uint32_t, ShapeC2D, "u32,C2D");
@@ -2578,6 +2719,8 @@ EnvLaunch select_env(const State& s, int nt, int epw) {
     return MC_EL(64, 2, uint64_t, Dynamic, "u64,generic");
   }
   if (narrow) {
+    if (nt == 64 && fits32 && spec && vt && ShapeC2V::matches(s)) return MC_EL(64, 1, uint32_t, ShapeC2V, "u32,C2");
+    if (nt == 64 && fits32 && spec && vt && ShapeC2DV::matches(s)) return MC_EL(64, 1, uint32_t, ShapeC2DV, "u32,C2D");
     if (nt == 64 && fits32 && spec && rp && ShapeC2::matches(s)) return MC_EL(64, 1, uint32_t, ShapeC2, "u32,C2");
     if (nt == 64 && fits32 && spec && rp && ShapeC2D::matches(s)) return MC_EL(64, 1, uint32_t, ShapeC2D, "u32,C2D");
     if (nt == 128 && spec && ShapeC5B::matches(s)) return MC_EL(128, 1, uint32_t, ShapeC5B, "u32,C5");
@@ -2592,6 +2735,16 @@ EnvLaunch select_env(const State& s, int nt, int epw) {
 #undef MC_EL
 
 const char* env_variant(const State& s, int nt, int epw) { return select_env(s, nt, epw).name; }
+
+// whether a step of this state would read the visibility table if the handle
+// had one (mc_capi.hip builds it only then)
+bool env_takes_vis_table(const State& s, int nt, int epw) {
+  State t = s;
+  t.vis_tab = nullptr;
+  const EnvLaunch without = select_env(t, nt, epw);
+  t.vis_tab = reinterpret_cast<const uint32_t*>(&t);  // any non-null value: select_env only tests it
+  return select_env(t, nt, epw).launch != without.launch;
+}
 
 hipError_t launch_env(const State& s, int mode, const uint8_t* actions, const uint8_t* env_mask,
                       const int32_t* inj_pos, double* reward, uint8_t* done, uint8_t* obs,

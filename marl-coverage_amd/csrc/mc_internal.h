@@ -191,6 +191,10 @@ struct State {
   // compiled sparse-beam kernels are then not selected): one row of
   // ray_prog_row_words words per lane of an env slot
   const uint32_t* ray_prog;
+  // The lidar's visibility table (mc_vistab.h; null: none, the kernels march):
+  // one 128-byte record of mark rows per (pool grid, cell), rebuilt whenever
+  // the pool or the beam table changes
+  const uint32_t* vis_tab;
 };
 
 // EnvRec's first / second 16 bytes as one load each, and their fields
@@ -413,12 +417,14 @@ __host__ __device__ inline size_t slot_stride(size_t slot_lds) {
 // to constants instead of living in SGPRs across the kernel.  BW: a bench
 // instantiation -- square padded grids of side BW (the tile geometry and the
 // beam-bit row length fold to constants) with the bench's episode flags (no
-// comm graph, grids kept on reset, auto-reset on).
+// comm graph, grids kept on reset, auto-reset on).  VT: the step reads its
+// lidar marks from the visibility table (State::vis_tab, set: select_env)
+// instead of marching.
 template <int N_, int H_, int NB_, int EGO_, int KM_, int KN_ = 0, int LC_ = 3, int DS_ = 0, int FN_ = 0,
-          int FS_ = 0, int FW_ = 0, int BW_ = 0>
+          int FS_ = 0, int FW_ = 0, int BW_ = 0, int VT_ = 0>
 struct Shape {
   static constexpr int N = N_, H = H_, NB = NB_, EGO = EGO_, KM = KM_, KN = KN_, LC = LC_, DS = DS_;
-  static constexpr int FN = FN_, FS = FS_, FW = FW_, BW = BW_;
+  static constexpr int FN = FN_, FS = FS_, FW = FW_, BW = BW_, VT = VT_;
   __host__ __device__ static bool matches(const State& s) {
     return (N_ == 0 || s.N == N_) && (H_ == 0 || s.H == H_) &&
            (NB_ == 0 || (s.sensor == 0 && s.nbeams == NB_)) &&
