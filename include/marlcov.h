@@ -242,20 +242,38 @@ int mc_step(void* env, const uint8_t* dev_actions, double* dev_reward,
 /* num_steps consecutive mc_step calls in one call: step k reads the action
  * bytes at dev_actions + k * actions_stride and writes reward / done / obs /
  * adjacency at their pointer + k * stride (byte strides; 0 = every step
- * overwrites the same buffer; dev_adj may be NULL).  Each step is launched
- * exactly as mc_step launches it (one env-kernel launch, plus the dist /
- * dijkstra launches of the config), stream-ordered.  For callers whose
- * actions are known ahead (open-loop rollouts, benchmarks): one FFI crossing
- * instead of num_steps.  Same semantics as the reference's step
- * (dec_grid_rl.py:91-169) applied num_steps times.  Strides are in bytes
- * (0: every step writes the same buffer); reward_stride must be a multiple of
- * 8.  Arguments are checked before anything is enqueued; if a launch of step
- * k fails, steps 0..k-1 are already enqueued (the env has advanced k steps)
- * and mc_last_error() names k. */
+ * overwrites the same buffer; dev_adj may be NULL).  Same semantics as the
+ * reference's step (dec_grid_rl.py:91-169) applied num_steps times: every
+ * step's outputs are written, whatever the strides, and after the call the
+ * handle's state is what num_steps mc_step calls leave.  For callers whose
+ * actions are known ahead (open-loop and scripted rollouts, replays,
+ * look-ahead from mc_copy_envs forks, benchmarks).
+ *   How the steps are launched: a config whose step is the env kernel alone
+ * (no map_sharing, dist_reward, dijkstra_input or mini_map_rad) runs up to S
+ * consecutive steps inside one env-kernel launch, ceil(num_steps / S)
+ * launches per call, stream-ordered; a workgroup steps its envs on without
+ * a kernel boundary in between.  S is MARLCOV_FUSE_STEPS, read at mc_create:
+ * default 64, clamped to 1..1024 (so no single kernel runs for long whatever
+ * num_steps is); 0 or 1 means one launch per step.  Every other config, and
+ * a -DMC_STAMPS build, launches each step exactly as mc_step does (one
+ * env-kernel launch plus the dist / dijkstra launches of the config).
+ *   Strides are in bytes; reward_stride must be a multiple of 8.  Arguments
+ * are checked before anything is enqueued, and a stride whose product with a
+ * step index overflows int64 is refused with MC_EINVAL.  If launch j fails,
+ * the steps of launches 0..j-1 are already enqueued (the env has advanced
+ * that many steps) and mc_last_error() names the first step not enqueued. */
 int mc_step_many(void* env, const uint8_t* dev_actions, int64_t actions_stride, int32_t num_steps,
                  double* dev_reward, int64_t reward_stride, uint8_t* dev_done, int64_t done_stride,
                  void* dev_obs, int64_t obs_stride, uint8_t* dev_adj, int64_t adj_stride,
                  void* stream);
+
+/* The number of env-kernel launches this handle has issued since mc_create
+ * (mc_reset, mc_step and mc_step_many all count; a fused mc_step_many launch
+ * of S steps counts once).  A host counter for tests and tools: it shows
+ * whether a call took the fused path.  Added without raising
+ * MARLCOV_ABI_VERSION: the addition changes no existing symbol or struct, and
+ * a binding built for version 12 without it keeps working. */
+int64_t mc_env_launches(void* env);
 
 /* Device-to-device copy of a state field into / out of caller memory.
  * `bytes` must equal the field size (mc_field_bytes). */

@@ -140,6 +140,7 @@ SIGNATURES = [
     ("mc_reset", ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
     ("mc_step", ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("mc_step_many", ctypes.c_int, [_VP, _VP, _I64, _I32, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _I64, _VP]),
+    ("mc_env_launches", _I64, [_VP]),
     ("mc_field_bytes", _I64, [_VP, _I32]),
     ("mc_get_state", ctypes.c_int, [_VP, _I32, _VP, _I64, _VP]),
     ("mc_set_state", ctypes.c_int, [_VP, _I32, _VP, _I64, _VP]),

@@ -260,7 +260,9 @@ class BatchCoverageEnv:
         return self.obs, self.reward, self.done
 
     def rollout(self, actions):
-        """Step K times with known actions, one C-ABI call (mc_step_many):
+        """Step K times with known actions, one C-ABI call (mc_step_many; a
+        config whose step is the env kernel alone runs up to
+        MARLCOV_FUSE_STEPS, default 64, steps per kernel launch):
         ``actions`` uint8 [K, B, N] device tensor; returns new tensors obs
         [K, B, N, Lc, E, E], reward [K, B], done [K, B] -- step k's outputs,
         exactly what K ``step`` calls would have returned, with the per-step
@@ -323,6 +325,14 @@ class BatchCoverageEnv:
     def kernel_variant(self) -> str:
         """The env-kernel instantiation mc_step launches (mc_kernel_variant)."""
         return self.lib.mc_kernel_variant(self._h).decode()
+
+    def env_launches(self) -> int:
+        """Env-kernel launches this handle has issued (mc_env_launches): a
+        fused ``rollout`` launch of several steps counts once."""
+        n = self.lib.mc_env_launches(self._h)
+        if n < 0:
+            _lib.check(int(n), "mc_env_launches")
+        return int(n)
 
     def dijkstra_variant(self) -> str:
         """The kernels of the dijkstra_input layer (mc_dijkstra_variant):

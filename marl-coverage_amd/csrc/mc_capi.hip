@@ -16,12 +16,14 @@
 #include "marlcov.h"
 #include "mc_internal.h"
 #include "mc_fork.h"
+#include "mc_fuse.h"
 #include "mc_vistab.h"
 
 namespace mc {
 hipError_t launch_env(const State& s, int mode, const uint8_t* actions, const uint8_t* env_mask,
                       const int32_t* inj_pos, double* reward, uint8_t* done, uint8_t* obs,
-                      uint8_t* adj, int nt, int epw, hipStream_t stream);
+                      uint8_t* adj, int num_steps, const EnvStrides& strides, int nt, int epw,
+                      hipStream_t stream);
 int env_pack(const State& s);
 hipError_t launch_share(const State& s, const uint8_t* actions, hipStream_t stream);
 hipError_t launch_rec_field(const State& s, int off, int width, void* buf, bool to_rec, hipStream_t stream);
@@ -78,6 +80,11 @@ struct Env {
   int device = 0;
   int nt = 128;
   int epw = 1;  // envs per workgroup (2: two envs share one wave)
+  // steps per env-kernel launch of a fused mc_step_many call (MARLCOV_FUSE_STEPS,
+  // read at mc_create; 1: one launch per step), and the env-kernel launches
+  // this handle has issued (mc_env_launches)
+  int fuse_steps = mc::kFuseStepsDefault;
+  int64_t env_launches = 0;
   size_t dj_lds = 0;  // dijkstra_input: LDS bytes of the BFS kernel
   uint32_t* dj_list = nullptr;  // dijkstra_input: count, done, last count + [B*N] items (full-map BFS)
   bool dj_window = true;        // dijkstra_input: window kernel first (MARLCOV_DJ_FULL=1: off)
@@ -332,6 +339,7 @@ int mc_create(const mc_config* cfg, int hip_device, void** out_env) {
   E->cfg = c;
   E->vis_mode = vis_mode;
   E->vis_cap = vis_cap;
+  E->fuse_steps = mc::fuse_steps_from_env(getenv("MARLCOV_FUSE_STEPS"));
   E->range = c.lidar_range;
   E->device = hip_device;
   mc::State& s = E->s;
@@ -1053,7 +1061,8 @@ int mc_reset(void* env, const uint8_t* dev_env_mask, const int32_t* dev_pos, voi
   if (rc) return rc;
   HIP_TRY(hipSetDevice(E->device));
   HIP_TRY(mc::launch_env(E->s, mc::MODE_RESET, nullptr, dev_env_mask, dev_pos, nullptr, nullptr,
-                         (uint8_t*)dev_obs, dev_adj, E->nt, launch_epw(E), (hipStream_t)stream));
+                         (uint8_t*)dev_obs, dev_adj, 1, mc::EnvStrides{}, E->nt, launch_epw(E), (hipStream_t)stream));
+  ++E->env_launches;
   rc = dijkstra_layer(E, dev_obs, (hipStream_t)stream);
   if (rc) return rc;
   return dist_terms(E, 1, (hipStream_t)stream);
@@ -1069,10 +1078,22 @@ static int step_once(Env* E, const uint8_t* dev_actions, double* dev_reward, uin
     if (rc) return rc;
   }
   HIP_TRY(mc::launch_env(E->s, mc::MODE_STEP, dev_actions, nullptr, nullptr, dev_reward, dev_done,
-                         (uint8_t*)dev_obs, dev_adj, E->nt, launch_epw(E), st));
+                         (uint8_t*)dev_obs, dev_adj, 1, mc::EnvStrides{}, E->nt, launch_epw(E), st));
+  ++E->env_launches;
   rc = dijkstra_layer(E, dev_obs, st);
   if (rc) return rc;
   return dist_terms(E, 1, st);
+}
+
+// mc_step_many runs several steps per env-kernel launch: the handle's step is
+// the env kernel alone (no launch before or after it reads or writes the maps)
+static bool fuses_steps(const Env* E) {
+#ifdef MC_STAMPS
+  return false;  // the phase stamps are per launch
+#else
+  return E->fuse_steps > 1 && !E->cfg.map_sharing && !E->cfg.dist_reward && !E->cfg.dijkstra_input &&
+         E->cfg.mini_map_rad == 0;
+#endif
 }
 
 int mc_step(void* env, const uint8_t* dev_actions, double* dev_reward, uint8_t* dev_done,
@@ -1100,6 +1121,29 @@ int mc_step_many(void* env, const uint8_t* dev_actions, int64_t actions_stride, 
   if (rc) return rc;
   HIP_TRY(hipSetDevice(E->device));
   hipStream_t st = (hipStream_t)stream;
+  const int64_t stride[mc::FUSE_BUFS] = {actions_stride, reward_stride, done_stride, obs_stride, adj_stride};
+  if (!mc::fuse_offsets_fit(num_steps, stride))
+    return fail(MC_EINVAL, "mc_step_many: a stride times the step count overflows int64");
+  if (fuses_steps(E)) {
+    // the step is the env kernel alone: up to fuse_steps steps per launch
+    const mc::EnvStrides es{actions_stride, reward_stride, done_stride, obs_stride, adj_stride};
+    const int64_t chunks = mc::fuse_chunk_count(num_steps, E->fuse_steps);
+    for (int64_t i = 0; i < chunks; ++i) {
+      mc::FuseChunk c;
+      if (!mc::fuse_chunk(num_steps, E->fuse_steps, i, stride, &c))
+        return fail(MC_EINVAL, "mc_step_many: chunk %lld of %lld", (long long)i, (long long)chunks);
+      const hipError_t he = mc::launch_env(
+          E->s, mc::MODE_STEP, dev_actions + c.off[mc::FUSE_ACTIONS], nullptr, nullptr,
+          reinterpret_cast<double*>(reinterpret_cast<char*>(dev_reward) + c.off[mc::FUSE_REWARD]),
+          dev_done + c.off[mc::FUSE_DONE], static_cast<uint8_t*>(dev_obs) + c.off[mc::FUSE_OBS],
+          dev_adj ? dev_adj + c.off[mc::FUSE_ADJ] : nullptr, c.count, es, E->nt, launch_epw(E), st);
+      if (he != hipSuccess)  // the launches before it are enqueued: the env has advanced c.first steps
+        return fail(MC_EHIP, "mc_step_many: step %lld of %d failed after %lld steps were enqueued: launch of %d steps: %s",
+                    (long long)c.first, (int)num_steps, (long long)c.first, (int)c.count, hipGetErrorString(he));
+      ++E->env_launches;
+    }
+    return MC_OK;
+  }
   for (int32_t k = 0; k < num_steps; ++k) {
     rc = step_once(E, dev_actions + k * actions_stride,
                    reinterpret_cast<double*>(reinterpret_cast<char*>(dev_reward) + k * reward_stride),
@@ -1112,6 +1156,12 @@ int mc_step_many(void* env, const uint8_t* dev_actions, int64_t actions_stride, 
     }
   }
   return MC_OK;
+}
+
+int64_t mc_env_launches(void* env) {
+  Env* E = as_env(env);
+  if (!E) return fail(MC_EINVAL, "mc_env_launches: null env");
+  return E->env_launches;
 }
 
 int64_t mc_field_bytes(void* env, int32_t f) {

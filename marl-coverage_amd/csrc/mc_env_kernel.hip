@@ -237,6 +237,7 @@ struct Ctx {
   static constexpr bool VISTAB = RAYPROG && SH::VT != 0 && vis_fits(SH::H) && 8 * SH::N <= LPE;
   uint32_t rp[RPW];  // RAYPROG: this lane's program row (round trip 1; VISTAB: a reset's only)
   int sub;    // lane within the env
+  int lane;   // lane within the wave
   int lane0;  // first lane of this env's slot within the wave
   int e;      // env index
   Lds<WT> L;
@@ -1249,7 +1250,7 @@ __device__ __forceinline__ void sense(const State& s, const CT& C) {
       fan_march(s, C);
       return;
     }
-    WT* sink = L.sink + (threadIdx.x & 63);
+    WT* sink = L.sink + C.lane;
     const uint32_t sink_m = (uint32_t)(uintptr_t)(const lds_char*)(const char*)sink -
                             (uint32_t)((L.fpr - L.negr) * (int)sizeof(WT));
     if constexpr (CT::RAYPROG) {
@@ -1435,7 +1436,7 @@ __device__ __forceinline__ void merge(const State& s, const CT& C, Items<CT::KI>
   }
   // EPW == 1: agent j's block origin in lane j of every wave, broadcast by
   // v_readlane (N <= 64)
-  const int jw = (int)(threadIdx.x & 63);
+  const int jw = C.lane;
   const int jl = jw < s.N ? jw : 0;
   const int abx = L.bx[jl], aby = L.by[jl];
   // EPW == 1 without a compile-time agent count <= 8 (C5: 16 agents):
@@ -1782,19 +1783,39 @@ struct EnvIO {
   uint8_t* obs_out;
   uint8_t* adj_out;  // null: no comm graph output
   int mode;
+  // fused steps (mc_step_many): the launch runs num_steps consecutive steps of
+  // every env; step k reads / writes the buffers above + k * stride (bytes)
+  int num_steps;
+  EnvStrides stride;
 };
 struct EnvArgs {
   State s;
   EnvIO io;
 };
+// the launch's buffers as step k of the launch sees them (k: wave-uniform)
+__device__ __forceinline__ EnvIO io_at_step(const EnvIO& a, int k) {
+  EnvIO r = a;
+  r.actions = a.actions + (int64_t)k * a.stride.actions;
+  r.reward_out = reinterpret_cast<double*>(reinterpret_cast<char*>(a.reward_out) + (int64_t)k * a.stride.reward);
+  r.done_out = a.done_out + (int64_t)k * a.stride.done;
+  r.obs_out = a.obs_out + (int64_t)k * a.stride.obs;
+  r.adj_out = a.adj_out ? a.adj_out + (int64_t)k * a.stride.adj : nullptr;
+  return r;
+}
+// the kernel arguments through an opaque pointer: loaded where they are used
+// (s_load, scalar cache) instead of staying live in SGPRs
+__device__ __forceinline__ const EnvArgs& kernarg_env_args() {
+  auto kp = __builtin_amdgcn_kernarg_segment_ptr();  // the EnvArgs
+  asm volatile("" : "+s"(kp));
+  return *(const EnvArgs*)kp;
+}
+// k: the step of the launch (the buffers' offsets are applied again)
 template <class SH, int EPW>
-__device__ __forceinline__ void reload_state(State& s, EnvIO& io) {
+__device__ __forceinline__ void reload_state(State& s, EnvIO& io, int k) {
   if constexpr (EPW == 1) {
-    auto kp = __builtin_amdgcn_kernarg_segment_ptr();  // the EnvArgs
-    asm volatile("" : "+s"(kp));
-    const EnvArgs& A = *(const EnvArgs*)kp;
+    const EnvArgs& A = kernarg_env_args();
     s = A.s;
-    io = A.io;
+    io = io_at_step(A.io, k);
     specialize<SH>(s);
   }
 }
@@ -2121,7 +2142,7 @@ __device__ __forceinline__ void write_obs_fast(const State& s, const CT& C, uint
   constexpr int D = EPW * DPE;           // dwords per wave
   const int e_first = blockIdx.x * EPW;  // the wave's first env
   uint32_t* out = reinterpret_cast<uint32_t*>(obs_out + (size_t)e_first * (NB * EE));
-  const int lane = (int)(threadIdx.x & 63);
+  const int lane = C.lane;
   // three dwords per lane when an env's run is whole triples and the wave's
   // triples fit 64 lanes (C2: 25 per env): one pair of ds_bpermutes and one
   // global_store_dwordx3 per lane; a triple's 12 bits span at most two crops
@@ -2179,28 +2200,18 @@ constexpr int env_min_waves() {
   return SH::N == 16 ? 4 : 1;
 }
 
-template <int NT, int EPW, typename WT, class SH>
-__global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvArgs args) {
-  State s = args.s;
-  specialize<SH>(s);
-  EnvIO io = args.io;
-  const int mode = io.mode;
-  using CT = Ctx<NT, EPW, WT, SH>;  // the instantiation's compile-time configuration (see Ctx)
+// One step (or the reset) of the slot's env: step k of the launch, with io the
+// launch's buffers as step k sees them (io_at_step).  `valid`: the slot has an
+// env (a short last workgroup's idle slot writes nothing, in any step).
+template <class CT>
+__device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool valid, const int k) {
+  using WT = typename CT::WT;
+  using SH = typename CT::SH;
+  constexpr int NT = CT::NT, EPW = CT::EPW;
   constexpr int LPE = CT::LPE, KI = CT::KI, NSM = CT::NSM;
   constexpr bool O32 = CT::O32, FRONT = CT::FRONT, EARLY = CT::EARLY, kPrePrefetch = CT::kPrePrefetch;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x;
+  const int mode = io.mode;
   const int N = s.N;
-  CT C;
-  const int slot = EPW == 1 ? 0 : tid / LPE;
-  C.sub = EPW == 1 ? tid : tid - slot * LPE;
-  C.lane0 = EPW == 1 ? 0 : slot * LPE;
-  const int e_raw = blockIdx.x * EPW + slot;
-  const bool valid = e_raw < s.B;  // a short last workgroup leaves a slot idle
-  C.e = valid ? e_raw : s.B - 1;
-  const size_t slot_lds =
-      state_lds_bytes(s, (int)sizeof(WT));
-  C.L = carve<WT>(smem + slot * slot_stride(slot_lds), s);
   const Lds<WT>& L = C.L;
   const int e = C.e;
 
@@ -2313,7 +2324,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
     for (int b = C.sub + LPE; b < s.nbeams; b += LPE) L.beams[b] = s.beams[b];
   }
   __syncthreads();
-  reload_state<SH, EPW>(s, io);
+  reload_state<SH, EPW>(s, io, k);
 
   if (active) {
     STAMP(1);
@@ -2375,7 +2386,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
     const int numfree = el<O32>(s.numfree, g0);
     __syncthreads();
     STAMP(2);
-    reload_state<SH, EPW>(s, io);
+    reload_state<SH, EPW>(s, io, k);
     // (the same loop on the scalar unit, robots read by v_readlane, was
     // slower: 10.17 vs 9.83 us at C2 -- +178 SALU for -17 VALU per wave)
     if constexpr (!FRONT && !EARLY) {  // (FRONT, EARLY: moved during round trip 2)
@@ -2395,7 +2406,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
       __syncthreads();
     }
     STAMP(3);
-    reload_state<SH, EPW>(s, io);
+    reload_state<SH, EPW>(s, io, k);
     // dist_reward: lane i < N loads its agent's PRE terms (the last step's
     // dist kernels wrote them) now that its move is known; they land during
     // the sensing (kPrePrefetch: compiled shapes)
@@ -2423,7 +2434,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
     sense_and_merge<CT, CT::VISTAB>(s, C, I);
     __syncthreads();
     STAMP(5);
-    reload_state<SH, EPW>(s, io);
+    reload_state<SH, EPW>(s, io, k);
     // every lane of the slot computes the reward and done (the same values:
     // no broadcast round trip or barrier before the stores); lane 0 stores
     bool do_reset;
@@ -2513,7 +2524,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
     // writes (one wave: its LDS operations complete in order)
     if constexpr (NT > 64) __syncthreads();
     STAMP(6);
-    reload_state<SH, EPW>(s, io);
+    reload_state<SH, EPW>(s, io, k);
     if (!do_reset) {
       store_tiles(s, C, I);
       STAMP(7);
@@ -2521,7 +2532,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
       reset_env(s, C, nullptr);  // the finished episode's tiles are not stored
     }
   } else if (reset_req || sent_reset) {
-    reload_state<SH, EPW>(s, io);
+    reload_state<SH, EPW>(s, io, k);
     if (C.sub == 0 && sentinel) sentinel_done(s, io, e, g0, free_old, currstep0);
     reset_env(s, C, reset_req ? io.inj_pos : nullptr);
     dlist = s.dist && C.sub < N;  // fresh maps: M unknown
@@ -2532,7 +2543,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
     // plane is scattered.  With the fan march the column planes overlay
     // fold / oold (carve), and a multi-wave slot's column-byte stores would
     // race with another wave's stage_fold stores.
-    reload_state<SH, EPW>(s, io);
+    reload_state<SH, EPW>(s, io, k);
     Items<KI> I;
     stage_load(s, C, g0, true, I);
     stage_fold(s, C, I);
@@ -2579,7 +2590,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
     const bool me = valid && dlist;
     const uint64_t m = __ballot(me);
     if (m) {
-      const int lane = (int)(threadIdx.x & 63);
+      const int lane = C.lane;
       const uint64_t slotm = LPE >= 64 ? ~0ull : (low_mask(LPE) << (lane & ~(LPE - 1) & 63));
       const uint64_t ms = m & slotm;
       if (ms) {
@@ -2599,7 +2610,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
     }
   }
   STAMP(8);
-  reload_state<SH, EPW>(s, io);
+  reload_state<SH, EPW>(s, io, k);
   if constexpr (CT::OBS_FAST) {
     if (MC_ABL != 4) write_obs_fast(s, C, io.obs_out);  // every lane of the workgroup
   } else {
@@ -2618,6 +2629,81 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
   STAMP(10);
+}
+
+// The launch runs io.num_steps consecutive steps (mc_step, mc_reset: 1;
+// mc_step_many's fused launches: up to MARLCOV_FUSE_STEPS).  An env is owned
+// by the same slot of the same workgroup in every step, and a step reads only
+// its env's state and read-only tables, so the workgroup runs step k + 1 right
+// after step k: no grid-wide synchronisation.  What step k + 1 re-reads of
+// this launch's stores -- pos, rec, the free / obstacle tiles (plain stores),
+// the union tiles (global_atomic_or, executed at L2), reset_env's cleared maps
+// -- was stored by this workgroup, so a workgroup-scope release / acquire
+// orders it (the release waits for the stores and atomics to be acknowledged;
+// the CU's L1 is write-through and shared by the workgroup's waves, and an
+// atomic leaves no stale copy of its line there -- tools/micro/loop_probe.hip
+// checks exactly that).  Several waves also meet at a barrier between the two
+// fences: a fast wave must not re-initialise LDS that a slow wave still reads
+// (the obs), and must not load state a slow wave has not stored yet.
+template <int NT, int EPW, typename WT, class SH>
+__global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvArgs args) {
+  using CT = Ctx<NT, EPW, WT, SH>;  // the instantiation's compile-time configuration (see Ctx)
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  // the lane's place in the workgroup: its env slot and the slot's LDS
+  auto place = [&](const State& s, int tid, CT& C) {
+    constexpr int LPE = CT::LPE;
+    C.lane = tid & 63;
+    const int slot = EPW == 1 ? 0 : tid / LPE;
+    C.sub = EPW == 1 ? tid : tid - slot * LPE;
+    C.lane0 = EPW == 1 ? 0 : slot * LPE;
+    const int e_raw = blockIdx.x * EPW + slot;
+    const bool valid = e_raw < s.B;  // a short last workgroup leaves a slot idle
+    C.e = valid ? e_raw : s.B - 1;
+    const size_t slot_lds =
+        state_lds_bytes(s, (int)sizeof(WT));
+    C.L = carve<WT>(smem + slot * slot_stride(slot_lds), s);
+    return valid;
+  };
+  // ---- step 0 (mc_step, mc_reset: the only one), straight-line: the kernel
+  // arguments as the compiler likes to load them, all at the entry
+  {
+    State s = args.s;
+    specialize<SH>(s);
+    EnvIO io = args.io;
+    CT C;
+    const bool valid = place(s, threadIdx.x, C);
+    env_step(s, io, C, valid, 0);
+  }
+  // ---- steps 1 .. num_steps - 1 of a fused launch: a second copy of the step
+  // in a loop.  (One copy, looped from step 0, made every launch slower: the
+  // loop keeps whatever is loop-invariant live in registers across the whole
+  // step -- C2 125 -> 206 VGPRs, 48 SGPRs spilled -- and with the arguments
+  // read inside the loop instead, a launch's first step waits for the cold
+  // kernel-argument lines one by one: mc_step 6.6 -> 8.0 us at C2,
+  // profiles/r12/fused_steps/.)
+  const int num_steps = kernarg_env_args().io.num_steps;
+  for (int k = 1; k < num_steps; ++k) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    if constexpr (NT > 64) __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    // the State and the buffers, read from the kernel arguments in every step
+    // (kernarg_env_args: opaque, so the loads stay inside the loop, next to
+    // their uses, instead of every field staying live in SGPRs across it;
+    // they hit the scalar cache now)
+    const EnvArgs& A = kernarg_env_args();
+    State s = A.s;
+    specialize<SH>(s);
+    EnvIO io = io_at_step(A.io, k);
+    // ... and the lane's place, derived again from an opaque lane id: nothing
+    // lane-dependent is loop-invariant to the compiler, which would otherwise
+    // hoist a step's addresses and masks out of the loop and keep them in
+    // registers across it
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    CT C;
+    const bool valid = place(s, tid, C);
+    env_step(s, io, C, valid, k);
+  }
 }
 
 // Envs per wave: two when an env fits 32 lanes (N <= 32, at most KI staged
@@ -2643,15 +2729,15 @@ struct EnvLaunch {
   const char* name;
   void (*launch)(const State& s, int mode, const uint8_t* actions, const uint8_t* env_mask,
                  const int32_t* inj_pos, double* reward, uint8_t* done, uint8_t* obs, uint8_t* adj,
-                 hipStream_t stream);
+                 int num_steps, const EnvStrides& strides, hipStream_t stream);
 };
 
 template <int T, int P, typename W, class SH>
 static void launch_one(const State& s, int mode, const uint8_t* actions, const uint8_t* env_mask,
                        const int32_t* inj_pos, double* reward, uint8_t* done, uint8_t* obs, uint8_t* adj,
-                       hipStream_t stream) {
+                       int num_steps, const EnvStrides& strides, hipStream_t stream) {
   const size_t slot_lds = state_lds_bytes(s, (int)sizeof(W));
-  const EnvArgs args{s, EnvIO{actions, env_mask, inj_pos, reward, done, obs, adj, mode}};
+  const EnvArgs args{s, EnvIO{actions, env_mask, inj_pos, reward, done, obs, adj, mode, num_steps, strides}};
   hipLaunchKernelGGL((env_kernel<T, P, W, SH>), dim3((s.B + P - 1) / P), dim3(T), slot_stride(slot_lds) * P,
                      stream, args);
 }
@@ -2748,8 +2834,11 @@ bool env_takes_vis_table(const State& s, int nt, int epw) {
 
 hipError_t launch_env(const State& s, int mode, const uint8_t* actions, const uint8_t* env_mask,
                       const int32_t* inj_pos, double* reward, uint8_t* done, uint8_t* obs,
-                      uint8_t* adj, int nt, int epw, hipStream_t stream) {
-  select_env(s, nt, epw).launch(s, mode, actions, env_mask, inj_pos, reward, done, obs, adj, stream);
+                      uint8_t* adj, int num_steps, const EnvStrides& strides, int nt, int epw,
+                      hipStream_t stream) {
+  if (num_steps < 1 || (mode != MODE_STEP && num_steps != 1)) return hipErrorInvalidValue;  // a reset is one pass
+  select_env(s, nt, epw).launch(s, mode, actions, env_mask, inj_pos, reward, done, obs, adj, num_steps, strides,
+                                stream);
   return hipGetLastError();
 }
 

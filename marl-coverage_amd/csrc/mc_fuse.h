@@ -1,0 +1,52 @@
+// mc_fuse.h — the chunks of a fused mc_step_many call (mc_capi.hip): K steps
+// run as ceil(K / S) env-kernel launches of at most S steps each, S from
+// MARLCOV_FUSE_STEPS.  Host arithmetic only (tests/native/fuse_chunks_check.cpp
+// runs it under sanitizers).  Not part of the public ABI.
+#pragma once
+#include <stdint.h>
+
+namespace mc {
+
+constexpr int kFuseStepsDefault = 64, kFuseStepsMax = 1024;
+
+// the five per-step buffers of mc_step_many, in this order everywhere
+enum { FUSE_ACTIONS = 0, FUSE_REWARD, FUSE_DONE, FUSE_OBS, FUSE_ADJ, FUSE_BUFS };
+
+// MARLCOV_FUSE_STEPS as given (null: unset) -> steps per launch, 1..kFuseStepsMax
+// (0 and 1: one launch per step)
+inline int fuse_steps_from_env(const char* v) {
+  if (!v || !*v) return kFuseStepsDefault;
+  long n = 0;
+  for (const char* p = v; *p >= '0' && *p <= '9' && n <= kFuseStepsMax; ++p) n = n * 10 + (*p - '0');
+  return n < 1 ? 1 : (n > kFuseStepsMax ? kFuseStepsMax : (int)n);
+}
+
+inline int64_t fuse_chunk_count(int64_t K, int S) { return K <= 0 ? 0 : (K + S - 1) / S; }
+
+struct FuseChunk {
+  int64_t first;           // the chunk's first step
+  int32_t count;           // its steps, 1..S
+  int64_t off[FUSE_BUFS];  // first * stride: byte offset of step `first` in each buffer
+};
+
+// every k * stride of a call of K steps fits int64 (strides >= 0): tested on
+// the largest, (K - 1) * stride, before anything is enqueued
+inline bool fuse_offsets_fit(int64_t K, const int64_t (&stride)[FUSE_BUFS]) {
+  if (K <= 1) return true;
+  for (int b = 0; b < FUSE_BUFS; ++b)
+    if (stride[b] < 0 || (stride[b] > 0 && K - 1 > INT64_MAX / stride[b])) return false;
+  return true;
+}
+
+// chunk i (0 <= i < fuse_chunk_count(K, S)) of K steps at S per launch; false
+// (nothing written) for an index outside the call or an offset past int64
+inline bool fuse_chunk(int64_t K, int S, int64_t i, const int64_t (&stride)[FUSE_BUFS], FuseChunk* c) {
+  if (S < 1 || i < 0 || i >= fuse_chunk_count(K, S) || !fuse_offsets_fit(K, stride)) return false;
+  c->first = i * S;  // < K
+  const int64_t left = K - c->first;
+  c->count = (int32_t)(left < S ? left : S);
+  for (int b = 0; b < FUSE_BUFS; ++b) c->off[b] = c->first * stride[b];
+  return true;
+}
+
+}  // namespace mc

@@ -11,6 +11,12 @@ namespace mc {
 
 enum Mode : int { MODE_STEP = 0, MODE_RESET = 1 };
 
+// Byte strides of an env-kernel launch that runs several steps (mc_step_many's
+// fused launches, mc_fuse.h): step k of the launch uses each buffer + k * stride
+struct EnvStrides {
+  int64_t actions = 0, reward = 0, done = 0, obs = 0, adj = 0;
+};
+
 // Device error bits (OR-ed into State::err, read by mc_check).
 enum : uint32_t {
   ERR_WINDOW = 1u << 0,     // a beam left its staged window (cannot happen:

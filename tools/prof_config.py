@@ -2,7 +2,7 @@
 per-wave SQ counters of the TIMED steps only.
 
     python tools/prof_config.py --config c4 [--steps 50 --warmup 5] [--out gpurun_out/prof_c4]
-        [--extra "--maxsteps 2000"] [--sq]
+        [--extra "--maxsteps 2000"] [--sq] [--fuse S]
 
 Runs, each in its own process under its own time limit (no --pmc pass is
 combined with a trace domain other than --kernel-trace, and every pass holds
@@ -19,6 +19,11 @@ reset launches do not enter the means, and writes summary.json:
   HBM bytes per step: read = 2 x FETCH_SIZE (gfx950 counts half of each 128-B
   request, MI355X_MICROARCH.md HBM section), write = WRITE_SIZE; per-wave SQ
   counters; per step: the sums over its kernels.
+--fuse S runs bench.py under MARLCOV_FUSE_STEPS=S (S must divide --steps): the
+timed region's env kernel is then steps / S dispatches of S steps each (the
+warm-up's mc_step calls stay one step per dispatch), and every figure of such
+a dispatch is divided by the steps it ran: per_step_us, bytes per step and the
+SQ counters per wave and step.
 """
 from __future__ import annotations
 
@@ -86,6 +91,7 @@ def main():
     ap.add_argument("--extra", default="")
     ap.add_argument("--out", default=None)
     ap.add_argument("--sq", action="store_true")
+    ap.add_argument("--fuse", type=int, default=0, help="MARLCOV_FUSE_STEPS for the runs (0: leave the environment)")
     ap.add_argument("--limit", type=int, default=240)
     ap.add_argument("--analyze-only", action="store_true", help="re-summarise the runs already under --out")
     args = ap.parse_args()
@@ -94,6 +100,10 @@ def main():
     bench = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu", "--config", args.config,
              "--steps", str(args.steps), "--warmup", str(args.warmup)] + args.extra.split()
     os.environ.setdefault("TMPDIR", "/tmp")
+    if args.fuse:
+        if args.steps % args.fuse:
+            ap.error("--fuse must divide --steps")
+        os.environ["MARLCOV_FUSE_STEPS"] = str(args.fuse)
     passes = [("pmc_fetch", "FETCH_SIZE"), ("pmc_write", "WRITE_SIZE")]
     if args.sq:
         passes += [("pmc_sq1", SQ1), ("pmc_sq2", SQ2)]
@@ -110,7 +120,8 @@ def main():
 
     K = args.steps
     tr = trace(os.path.join(out, "trace"))
-    summary = {"config": args.config, "steps": K, "warmup": args.warmup, "bench_args": bench[2:], "kernels": {}}
+    summary = {"config": args.config, "steps": K, "warmup": args.warmup, "fuse_steps": args.fuse,
+               "bench_args": bench[2:], "kernels": {}}
     counters = {}
     for d, _ in passes:
         for k, lst in per_dispatch(os.path.join(out, d)).items():
@@ -119,20 +130,34 @@ def main():
     for k, durs in tr.items():
         # a per-step kernel runs in every warmup and timed step; the rest are
         # setup (grids, allocation fills), resets or action staging
-        if len(durs) < K + args.warmup or "random_actions" in k or k.startswith("__amd_rocclr"):
+        if "random_actions" in k or k.startswith("__amd_rocclr"):
             continue
-        # dispatches per step (C5's transform kernel runs twice: modes 2 and
-        # 3); a reset's extra dispatches do not change the rounding
-        m = max(1, round(len(durs) / (K + args.warmup)))
-        timed = durs[-K * m:]
-        ent = {"dispatches_total": len(durs), "dispatches_per_step": m, "timed_dispatches": K * m,
-               "mean_us": round(statistics.mean(timed), 3), "median_us": round(statistics.median(timed), 3),
-               "per_step_us": round(statistics.mean(timed) * m, 3)}
+        # an env kernel whose timed dispatches ran --fuse steps each: K / fuse
+        # dispatches after the warm-up's (one step each) and the reset's
+        fused = (args.fuse > 1 and "env_kernel" in k and len(durs) < K + args.warmup
+                 and len(durs) >= K // args.fuse + args.warmup)
+        if len(durs) < K + args.warmup and not fused:
+            continue
+        if fused:
+            nd, spd = K // args.fuse, args.fuse  # timed dispatches, steps per dispatch
+            timed = durs[-nd:]
+            ent = {"dispatches_total": len(durs), "steps_per_dispatch": spd, "timed_dispatches": nd,
+                   "mean_us": round(statistics.mean(timed), 3), "median_us": round(statistics.median(timed), 3),
+                   "per_step_us": round(sum(timed) / K, 3)}
+        else:
+            # dispatches per step (C5's transform kernel runs twice: modes 2 and
+            # 3); a reset's extra dispatches do not change the rounding
+            m = max(1, round(len(durs) / (K + args.warmup)))
+            nd, spd = K * m, 1
+            timed = durs[-nd:]
+            ent = {"dispatches_total": len(durs), "dispatches_per_step": m, "timed_dispatches": nd,
+                   "mean_us": round(statistics.mean(timed), 3), "median_us": round(statistics.median(timed), 3),
+                   "per_step_us": round(statistics.mean(timed) * m, 3)}
         c = counters.get(k, {})
         if "pmc_fetch" in c and "pmc_write" in c:
             # bytes per step: the timed dispatches' sum over K
-            f = [x["FETCH_SIZE"] for _, x in c["pmc_fetch"][-K * m:]]
-            w = [x["WRITE_SIZE"] for _, x in c["pmc_write"][-K * m:]]
+            f = [x["FETCH_SIZE"] for _, x in c["pmc_fetch"][-nd:]]
+            w = [x["WRITE_SIZE"] for _, x in c["pmc_write"][-nd:]]
             ent["hbm_read_bytes"] = round(2 * 1024 * sum(f) / K)
             ent["hbm_write_bytes"] = round(1024 * sum(w) / K)
             ent["hbm_bytes"] = ent["hbm_read_bytes"] + ent["hbm_write_bytes"]
@@ -140,13 +165,14 @@ def main():
         sq = {}
         for d in ("pmc_sq1", "pmc_sq2"):
             if d in c:
-                lst = c[d][-K * m:]
+                lst = c[d][-nd:]
                 for name in lst[0][1]:
                     sq[name] = statistics.median(x[name] for _, x in lst)
         if sq:
             waves = sq.get("SQ_WAVES", 1.0) or 1.0
             ent["sq_median"] = {n: v for n, v in sorted(sq.items())}
-            ent["sq_per_wave"] = {n: round(v / waves, 1) for n, v in sorted(sq.items()) if n != "SQ_WAVES"}
+            # (a wave of a fused dispatch lives spd steps: per wave and step)
+            ent["sq_per_wave"] = {n: round(v / waves / spd, 1) for n, v in sorted(sq.items()) if n != "SQ_WAVES"}
         step["mean_us"] += ent["per_step_us"]
         summary["kernels"][short(k)] = ent
     summary["step"] = {k: round(v, 3) for k, v in step.items()}
