@@ -437,6 +437,45 @@ int mc_sg_reset(void* env, const uint8_t* dev_env_mask, const int32_t* dev_pos, 
  * float64 [B] and done uint8 [B], and updates the registered state buffers. */
 int mc_sg_step(void* env, const uint8_t* dev_actions, const int32_t* dev_quot, double* dev_reward,
                uint8_t* dev_done, void* stream);
+
+/* num_steps consecutive mc_sg_step calls in one call (mc_step_many for
+ * SuperGridRL handles): step k reads its action bytes at dev_actions + k *
+ * actions_stride and its quotients at dev_quot + k * quot_stride (dev_quot may
+ * be NULL: all 0), and writes reward / done at their pointer + k * stride.
+ * Strides are in bytes; 0 = every step uses the same buffer; reward_stride
+ * must be a multiple of 8 and quot_stride of 4.  After the call the handle's
+ * state is exactly what num_steps mc_sg_step calls leave: the registered
+ * planes and dist buffers, the episode records (EP_PC / EP_LEN), a_prev, and
+ * the auto-reset start-cell stream.  Every step's reward and done are written;
+ * only the per-step STATE PLANES are not returned -- the registered buffers are
+ * state, and hold the state after the last step.  For planners that look ahead
+ * from mc_sg_copy_envs forks with known action sequences.
+ *   How the steps are launched.  Without dist_reward a step never reads the
+ * distance layer, so up to S consecutive steps run inside one step-kernel
+ * launch (a wave steps its envs on without a kernel boundary), ceil(num_steps /
+ * S) launches per call, and ONE distance-kernel launch follows the last of them
+ * and rewrites the whole layer (one more goes in front when an upload left the
+ * layers behind the maps, as in mc_sg_step).  S is MARLCOV_FUSE_STEPS, read at
+ * mc_sg_create, parsed and clamped as for mc_step_many: default 64, 1..1024;
+ * 0 or 1 means one step-kernel launch per step, still with the single final
+ * transform.  With dist_reward every step reads the layer the step before it
+ * wrote: each step is launched exactly as mc_sg_step launches it (step kernel
+ * plus transform), and the call saves only the host crossings.
+ *   Arguments are checked before anything is enqueued: a null env, actions,
+ * reward or done pointer, num_steps < 0, a negative or misaligned stride, or a
+ * stride whose product with a step index overflows int64 return MC_EINVAL.
+ * num_steps == 0 enqueues nothing and returns MC_OK.  If launch j fails, the
+ * steps of launches 0..j-1 are already enqueued (the env has advanced that many
+ * steps) and mc_last_error() names the first step not enqueued.  Added without
+ * raising MARLCOV_ABI_VERSION, like mc_env_launches. */
+int mc_sg_step_many(void* env, const uint8_t* dev_actions, int64_t actions_stride, const int32_t* dev_quot,
+                    int64_t quot_stride, int32_t num_steps, double* dev_reward, int64_t reward_stride,
+                    uint8_t* dev_done, int64_t done_stride, void* stream);
+/* Kernel launches this handle has issued since mc_sg_create: which = 0 the
+ * step-kernel launches (a fused launch of S steps counts once), 1 the
+ * distance-kernel launches (mc_sg_reset's included); any other `which`, or a
+ * null env, returns -1 and sets the error.  A host counter for tests and tools. */
+int64_t mc_sg_launches(void* env, int32_t which);
 int64_t mc_sg_field_bytes(void* env, int32_t field);
 int mc_sg_get_state(void* env, int32_t field, void* dev_dst, int64_t bytes, void* stream);
 /* Uploads mark the state buffers for a full rewrite at the next call. */

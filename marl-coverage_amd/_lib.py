@@ -158,6 +158,8 @@ SIGNATURES = [
     ("mc_sg_set_obs", ctypes.c_int, [_VP, _VP, _VP]),
     ("mc_sg_reset", ctypes.c_int, [_VP, _VP, _VP, _VP]),
     ("mc_sg_step", ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
+    ("mc_sg_step_many", ctypes.c_int, [_VP, _VP, _I64, _VP, _I64, _I32, _VP, _I64, _VP, _I64, _VP]),
+    ("mc_sg_launches", _I64, [_VP, _I32]),
     ("mc_sg_field_bytes", _I64, [_VP, _I32]),
     ("mc_sg_get_state", ctypes.c_int, [_VP, _I32, _VP, _I64, _VP]),
     ("mc_sg_set_state", ctypes.c_int, [_VP, _I32, _VP, _I64, _VP]),

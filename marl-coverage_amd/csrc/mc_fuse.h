@@ -1,7 +1,9 @@
 // mc_fuse.h — the chunks of a fused mc_step_many call (mc_capi.hip): K steps
 // run as ceil(K / S) env-kernel launches of at most S steps each, S from
 // MARLCOV_FUSE_STEPS.  Host arithmetic only (tests/native/fuse_chunks_check.cpp
-// runs it under sanitizers).  Not part of the public ABI.
+// runs it under sanitizers).  Not part of the public ABI.  mc_sg_step_many
+// (mc_super.hip) chunks its step-kernel launches with the same arithmetic: its
+// quotients take the FUSE_OBS slot, and FUSE_ADJ stays at stride 0.
 #pragma once
 #include <stdint.h>
 

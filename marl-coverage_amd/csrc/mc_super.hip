@@ -20,6 +20,11 @@
 //                   distance_map (:117-118): _free does not change between
 //                   get_state and the next get_distance_map, so the step
 //                   kernel reads its dist terms from it (no second transform).
+// mc_sg_step_many runs K steps in one call.  Without dist_reward the step
+// kernels never read the dist layer, so it launches sg_step_loop -- the same
+// step functions in a loop, up to MARLCOV_FUSE_STEPS steps per launch -- and
+// the distance kernel once, after the last step; with dist_reward it launches
+// every step as mc_sg_step does.
 // Maps are row bitboards: uint64 [W][RW], RW = ceil(L/64); bits >= L of a
 // row's last word are always 0.
 //
@@ -40,6 +45,7 @@
 #include "marlcov.h"
 #include "mc_device.h"
 #include "mc_fork.h"
+#include "mc_fuse.h"
 
 namespace mc {
 void set_last_error(const char* msg);
@@ -247,17 +253,22 @@ __global__ __launch_bounds__(256) void sg_reset_kernel(SState s, const uint8_t* 
 // in a single round together with the target's dist value, and the post-move
 // window comes from registers (one load round instead of one per window row,
 // twice).  R < 0: any radius, rows loaded as the loops reach them.
+//
+// The step is a __device__ function of the lane's thread id `tid` and the
+// workgroup's LDS rows, shared by the one-step kernel (sg_step_kernel) and the
+// fused loop (sg_step_loop, below).
 template <int R, int GPW>
-__global__ __launch_bounds__(256) void sg_step_kernel(SState s, const uint8_t* __restrict__ actions,
-                                                      const int32_t* __restrict__ quot,
-                                                      double* __restrict__ reward,
-                                                      uint8_t* __restrict__ done) {
+__device__ __forceinline__ void sg_step_lanes(const SState& s, const unsigned tid,
+                                              const uint8_t* __restrict__ actions,
+                                              const int32_t* __restrict__ quot, double* __restrict__ reward,
+                                              uint8_t* __restrict__ done,
+                                              double (&s_v)[kEnvsPerBlock * GPW][64 / GPW],
+                                              int (&s_x)[kEnvsPerBlock * GPW][64 / GPW],
+                                              int (&s_y)[kEnvsPerBlock * GPW][64 / GPW]) {
   constexpr int NG = 64 / GPW;  // lanes per env
-  __shared__ double s_v[kEnvsPerBlock * GPW][NG];
-  __shared__ int s_x[kEnvsPerBlock * GPW][NG], s_y[kEnvsPerBlock * GPW][NG];
-  const int lane = threadIdx.x & 63;
+  const int lane = tid & 63;
   const int grp = GPW == 1 ? 0 : lane / NG, li = GPW == 1 ? lane : lane & (NG - 1), gb = grp * NG;
-  const int slot_env = (threadIdx.x >> 6) * GPW + grp;  // env slot within the block
+  const int slot_env = (tid >> 6) * GPW + grp;  // env slot within the block
   const int e_raw = blockIdx.x * (kEnvsPerBlock * GPW) + slot_env;
   const bool valid = e_raw < s.B;
   const int e = valid ? e_raw : s.B - 1;
@@ -529,7 +540,7 @@ __global__ __launch_bounds__(256) void sg_step_kernel(SState s, const uint8_t* _
   uint64_t rs = __ballot(s.auto_reset && valid && li == 0 && dn != 0);
   if (rs) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the step's map ORs land first
-    const int e0 = blockIdx.x * (kEnvsPerBlock * GPW) + (int)(threadIdx.x >> 6) * GPW;
+    const int e0 = blockIdx.x * (kEnvsPerBlock * GPW) + (int)(tid >> 6) * GPW;
     for (; rs; rs &= rs - 1) {
       const int gj = (__ffsll((unsigned long long)rs) - 1) / NG;
       sg_reset_env(s, e0 + gj, lane, nullptr);
@@ -574,19 +585,20 @@ __device__ __forceinline__ int row_sum_to_lane0(int v) {
 }
 
 template <int R, int GPW>
-__global__ __launch_bounds__(256) void sg_step_rows(SState s, const uint8_t* __restrict__ actions,
-                                                    const int32_t* __restrict__ quot,
-                                                    double* __restrict__ reward,
-                                                    uint8_t* __restrict__ done) {
+__device__ __forceinline__ void sg_step_rows_body(const SState& s, const unsigned tid,
+                                                  const uint8_t* __restrict__ actions,
+                                                  const int32_t* __restrict__ quot, double* __restrict__ reward,
+                                                  uint8_t* __restrict__ done,
+                                                  double (&s_v)[kEnvsPerBlock * GPW][64 / GPW],
+                                                  int (&s_x)[kEnvsPerBlock * GPW][64 / GPW],
+                                                  int (&s_y)[kEnvsPerBlock * GPW][64 / GPW]) {
   static_assert(R >= 1 && 2 * R + 1 <= 8, "compiled radius: a row's masks fit 8 bits");
   constexpr int NG = 64 / GPW;  // lanes per env
   constexpr int n = 2 * R + 1;  // window rows / columns
   constexpr int RPL = 2;        // window rows per lane (RL >= 4, n <= 7)
-  __shared__ double s_v[kEnvsPerBlock * GPW][NG];
-  __shared__ int s_x[kEnvsPerBlock * GPW][NG], s_y[kEnvsPerBlock * GPW][NG];
-  const int lane = threadIdx.x & 63;
+  const int lane = tid & 63;
   const int grp = GPW == 1 ? 0 : lane / NG, li = GPW == 1 ? lane : lane & (NG - 1), gb = grp * NG;
-  const int slot_env = (threadIdx.x >> 6) * GPW + grp;
+  const int slot_env = (tid >> 6) * GPW + grp;
   const int e_raw = blockIdx.x * (kEnvsPerBlock * GPW) + slot_env;
   const bool valid = e_raw < s.B;
   const int e = valid ? e_raw : s.B - 1;
@@ -902,12 +914,103 @@ __global__ __launch_bounds__(256) void sg_step_rows(SState s, const uint8_t* __r
   uint64_t rs = __ballot(s.auto_reset && valid && li == 0 && dn != 0);
   if (rs) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the step's map ORs land first
-    const int e0 = blockIdx.x * (kEnvsPerBlock * GPW) + (int)(threadIdx.x >> 6) * GPW;
+    const int e0 = blockIdx.x * (kEnvsPerBlock * GPW) + (int)(tid >> 6) * GPW;
     for (; rs; rs &= rs - 1) {
       const int gj = (__ffsll((unsigned long long)rs) - 1) / NG;
       sg_reset_env(s, e0 + gj, lane, nullptr);
     }
   }
+}
+
+// --------------------------------------------------------------------------
+// The kernels of the two step functions: one step per launch (mc_sg_step), and
+// a loop of consecutive steps (mc_sg_step_many without dist_reward).
+// --------------------------------------------------------------------------
+template <int R, int GPW>
+__global__ __launch_bounds__(256) void sg_step_kernel(SState s, const uint8_t* __restrict__ actions,
+                                                      const int32_t* __restrict__ quot,
+                                                      double* __restrict__ reward,
+                                                      uint8_t* __restrict__ done) {
+  __shared__ double s_v[kEnvsPerBlock * GPW][64 / GPW];
+  __shared__ int s_x[kEnvsPerBlock * GPW][64 / GPW], s_y[kEnvsPerBlock * GPW][64 / GPW];
+  sg_step_lanes<R, GPW>(s, threadIdx.x, actions, quot, reward, done, s_v, s_x, s_y);
+}
+
+template <int R, int GPW>
+__global__ __launch_bounds__(256) void sg_step_rows(SState s, const uint8_t* __restrict__ actions,
+                                                    const int32_t* __restrict__ quot,
+                                                    double* __restrict__ reward,
+                                                    uint8_t* __restrict__ done) {
+  __shared__ double s_v[kEnvsPerBlock * GPW][64 / GPW];
+  __shared__ int s_x[kEnvsPerBlock * GPW][64 / GPW], s_y[kEnvsPerBlock * GPW][64 / GPW];
+  sg_step_rows_body<R, GPW>(s, threadIdx.x, actions, quot, reward, done, s_v, s_x, s_y);
+}
+
+// the arguments of a fused launch: step k of the launch reads / writes its
+// buffers at pointer + k * stride (bytes)
+struct SgLoopArgs {
+  SState s;
+  const uint8_t* actions;
+  const int32_t* quot;  // nullable
+  double* reward;
+  uint8_t* done;
+  int64_t actions_stride, quot_stride, reward_stride, done_stride;
+  int32_t num_steps;
+};
+
+__device__ __forceinline__ const SgLoopArgs& kernarg_sg_loop() {
+  auto kp = __builtin_amdgcn_kernarg_segment_ptr();  // the SgLoopArgs
+  asm volatile("" : "+s"(kp));
+  return *(const SgLoopArgs*)kp;
+}
+
+// num_steps consecutive steps in one launch, no distance transform in between
+// (without dist_reward a step never reads the distance layer).  A wave owns the
+// same envs in every step, each env group the same lanes, and the LDS rows are
+// indexed by the wave's own env slots, so step k + 1 follows step k inside the
+// wave: no barrier, no grid-wide synchronisation.  What step k + 1 re-reads of
+// step k's stores -- pos and the per-env scalars (plain stores), cov / obst
+// (atomic ORs, executed at L2), the maps sg_reset_env cleared -- was stored by
+// this wave, so a workgroup-scope release / acquire orders it (the CU's L1 is
+// write-through, and an atomic leaves no stale copy of its line there:
+// tools/micro/loop_probe.hip, as in the env kernel's fused loop).
+//   The arguments and the lane's place are derived again in every step from
+// opaque values, so nothing step-invariant stays live in registers across the
+// step (the env kernel's loop spilled when it did).
+//   sg_erode_kernel's region write is exact only one step after the layer was
+// written: every env stepped here gets dist_M = -1 ("unknown"), which makes
+// the transform that follows the call rewrite its whole layer.  A reset inside
+// the loop leaves full[e] = 1 while later steps store into the planes; only
+// the transform reads and clears `full`, and then rewrites them whole.
+template <bool ROWS, int R, int GPW>
+__global__ __launch_bounds__(256) void sg_step_loop(SgLoopArgs args) {
+  (void)args;
+  __shared__ double s_v[kEnvsPerBlock * GPW][64 / GPW];
+  __shared__ int s_x[kEnvsPerBlock * GPW][64 / GPW], s_y[kEnvsPerBlock * GPW][64 / GPW];
+  const int num_steps = kernarg_sg_loop().num_steps;
+  for (int k = 0; k < num_steps; ++k) {
+    if (k) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+    const SgLoopArgs& A = kernarg_sg_loop();
+    unsigned tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const uint8_t* actions = A.actions + k * A.actions_stride;
+    const int32_t* quot =
+        A.quot ? reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(A.quot) + k * A.quot_stride) : nullptr;
+    double* reward = reinterpret_cast<double*>(reinterpret_cast<char*>(A.reward) + k * A.reward_stride);
+    uint8_t* done = A.done + k * A.done_stride;
+    if constexpr (ROWS)
+      sg_step_rows_body<R, GPW>(A.s, tid, actions, quot, reward, done, s_v, s_x, s_y);
+    else
+      sg_step_lanes<R, GPW>(A.s, tid, actions, quot, reward, done, s_v, s_x, s_y);
+  }
+  const SgLoopArgs& A = kernarg_sg_loop();
+  constexpr int NG = 64 / GPW;
+  const int lane = threadIdx.x & 63;
+  const int e = blockIdx.x * (kEnvsPerBlock * GPW) + (int)(threadIdx.x >> 6) * GPW + (GPW == 1 ? 0 : lane / NG);
+  if (e < A.s.B && (GPW == 1 ? lane : lane & (NG - 1)) == 0) A.s.dist_M[e] = -1;
 }
 
 // --------------------------------------------------------------------------
@@ -1238,16 +1341,19 @@ int sg_fail(int code, const char* fmt, ...) {
 // Every step kernel mc_sg_step can launch, with the name mc_sg_kernel_variant
 // and mc_sg_kernel_name report for it.
 using SgStepFn = decltype(&mcs::sg_step_kernel<-1, 1>);
+using SgLoopFn = decltype(&mcs::sg_step_loop<false, -1, 1>);
 struct SgKernel {
   const char* name;
   SgStepFn fn;
+  SgLoopFn loop;  // the same step in a loop: mc_sg_step_many's fused launches
   bool rows;  // sg_step_rows (else sg_step_kernel: one lane per robot)
   int R;      // compiled radius, -1 = the runtime radius
   int gpw;    // envs per wave
 };
-#define SG_LANE(R, G) {"sg_step_kernel<" #R "," #G ">", mcs::sg_step_kernel<R, G>, false, R, G}
+#define SG_LANE(R, G) \
+  {"sg_step_kernel<" #R "," #G ">", mcs::sg_step_kernel<R, G>, mcs::sg_step_loop<false, R, G>, false, R, G}
 #define SG_LANES(R) SG_LANE(R, 1), SG_LANE(R, 2), SG_LANE(R, 4), SG_LANE(R, 8), SG_LANE(R, 16)
-#define SG_ROW(R, G) {"sg_step_rows<" #R "," #G ">", mcs::sg_step_rows<R, G>, true, R, G}
+#define SG_ROW(R, G) {"sg_step_rows<" #R "," #G ">", mcs::sg_step_rows<R, G>, mcs::sg_step_loop<true, R, G>, true, R, G}
 #define SG_ROWS(R) SG_ROW(R, 1), SG_ROW(R, 2), SG_ROW(R, 4), SG_ROW(R, 8)
 const SgKernel kSgKernels[] = {SG_LANES(-1), SG_LANES(1), SG_LANES(2), SG_LANES(3),
                                SG_ROWS(1),   SG_ROWS(2),  SG_ROWS(3)};
@@ -1274,6 +1380,8 @@ struct SgEnv {
   bool force_generic = false;  // MARLCOV_SG_GENERIC=1: A/B against the runtime-radius kernel
   bool force_sweep = false;    // MARLCOV_SG_SWEEP=1: A/B against the sweep kernel
   const SgKernel* step = nullptr;  // what mc_sg_step launches (sg_select, at create)
+  int fuse_steps = mc::kFuseStepsDefault;  // steps per fused launch (MARLCOV_FUSE_STEPS, at create)
+  int64_t step_launches = 0, dist_launches = 0;  // mc_sg_launches
   std::vector<void*> allocs;
 };
 
@@ -1346,16 +1454,29 @@ int sg_ready(SgEnv* E, const char* who) {
 }
 
 hipError_t launch_dist(SgEnv* E, hipStream_t st) {
-  if (E->erode) {
-    hipLaunchKernelGGL(mcs::sg_erode_kernel, dim3(E->s.B), dim3(256), E->erode_lds, st, E->s);
-    return hipGetLastError();
-  }
   const size_t lds = E->lds ? (size_t)E->s.W * E->pitch * 2 : 0;
-  if (E->lds)
+  if (E->erode)
+    hipLaunchKernelGGL(mcs::sg_erode_kernel, dim3(E->s.B), dim3(256), E->erode_lds, st, E->s);
+  else if (E->lds)
     hipLaunchKernelGGL(mcs::sg_dist_kernel<true>, dim3(E->s.B), dim3(E->dist_nt), lds, st, E->s, E->pitch);
   else
     hipLaunchKernelGGL(mcs::sg_dist_kernel<false>, dim3(E->s.B), dim3(E->dist_nt), 0, st, E->s, E->pitch);
-  return hipGetLastError();
+  const hipError_t he = hipGetLastError();
+  if (he == hipSuccess) ++E->dist_launches;
+  return he;
+}
+
+// one step exactly as mc_sg_step launches it: the step kernel, then the transform
+hipError_t launch_step(SgEnv* E, const uint8_t* actions, const int32_t* quot, double* reward, uint8_t* done,
+                       hipStream_t st) {
+  const SgKernel& k = *E->step;
+  const int per_block = mcs::kEnvsPerBlock * k.gpw;
+  const int blocks = (E->s.B + per_block - 1) / per_block;
+  hipLaunchKernelGGL(k.fn, dim3(blocks), dim3(64 * mcs::kEnvsPerBlock), 0, st, E->s, actions, quot, reward, done);
+  const hipError_t he = hipGetLastError();
+  if (he != hipSuccess) return he;
+  ++E->step_launches;
+  return launch_dist(E, st);
 }
 
 int check_numpos(SgEnv* E, hipStream_t st) {
@@ -1425,6 +1546,8 @@ int mc_sg_create(const mc_sg_config* cfg, int hip_device, void** out_env) {
     E->force_generic = ge && atoi(ge) == 1;
     const char* sw = getenv("MARLCOV_SG_SWEEP");
     E->force_sweep = sw && atoi(sw) == 1;
+    // steps per fused mc_sg_step_many launch: mc_step_many's variable, parser and limits
+    E->fuse_steps = mc::fuse_steps_from_env(getenv("MARLCOV_FUSE_STEPS"));
   }
   E->step = sg_select(E);
   if (!E->step) {
@@ -1591,15 +1714,88 @@ int mc_sg_step(void* env, const uint8_t* dev_actions, const int32_t* dev_quot, d
   hipStream_t st = (hipStream_t)stream;
   SG_TRY(hipSetDevice(E->device));
   if (E->stale) SG_TRY(launch_dist(E, st));  // the pre-move distance_map of the current maps
-  const SgKernel& k = *E->step;
-  const int per_block = mcs::kEnvsPerBlock * k.gpw;
+  SG_TRY(launch_step(E, dev_actions, dev_quot, dev_reward, dev_done, st));
+  E->stale = false;
+  return MC_OK;
+}
+
+int mc_sg_step_many(void* env, const uint8_t* dev_actions, int64_t actions_stride, const int32_t* dev_quot,
+                    int64_t quot_stride, int32_t num_steps, double* dev_reward, int64_t reward_stride,
+                    uint8_t* dev_done, int64_t done_stride, void* stream) {
+  SgEnv* E = as_sg(env);
+  if (!E || !dev_actions || !dev_reward || !dev_done) return sg_fail(MC_EINVAL, "mc_sg_step_many: null argument");
+  if (num_steps < 0 || actions_stride < 0 || quot_stride < 0 || reward_stride < 0 || done_stride < 0)
+    return sg_fail(MC_EINVAL, "mc_sg_step_many: negative step count or stride");
+  if (reward_stride % 8 != 0) return sg_fail(MC_EINVAL, "mc_sg_step_many: reward_stride must be a multiple of 8 bytes");
+  if (quot_stride % 4 != 0) return sg_fail(MC_EINVAL, "mc_sg_step_many: quot_stride must be a multiple of 4 bytes");
+  // mc_fuse.h's five per-step buffers: the quotients ride in the obs slot, the last stays unused
+  const int64_t stride[mc::FUSE_BUFS] = {actions_stride, reward_stride, done_stride, quot_stride, 0};
+  if (!mc::fuse_offsets_fit(num_steps, stride))
+    return sg_fail(MC_EINVAL, "mc_sg_step_many: a stride times the step count overflows int64");
+  int rc = sg_ready(E, "mc_sg_step_many");
+  if (rc) return rc;
+  if (num_steps == 0) return MC_OK;
+  hipStream_t st = (hipStream_t)stream;
+  SG_TRY(hipSetDevice(E->device));
+  if (E->stale) SG_TRY(launch_dist(E, st));  // as mc_sg_step: the layers of the current maps
+  E->stale = false;
+  auto at = [](auto* p, int64_t off) { return reinterpret_cast<decltype(p)>(reinterpret_cast<uintptr_t>(p) + off); };
+  if (E->s.dist) {
+    // every step reads the layer the step before it wrote: launched as mc_sg_step launches it
+    for (int32_t k = 0; k < num_steps; ++k) {
+      const hipError_t he = launch_step(E, at(dev_actions, k * actions_stride),
+                                        dev_quot ? at(dev_quot, k * quot_stride) : nullptr,
+                                        at(dev_reward, k * reward_stride), at(dev_done, k * done_stride), st);
+      if (he != hipSuccess) {  // steps 0..k-1 are enqueued: the env has advanced k steps
+        E->stale = true;       // (a step kernel without its transform leaves the layer behind the maps)
+        return sg_fail(MC_EHIP, "mc_sg_step_many: step %d of %d failed after %d steps were enqueued: %s", (int)k,
+                       (int)num_steps, (int)k, hipGetErrorString(he));
+      }
+    }
+    return MC_OK;
+  }
+  // the step kernels never read the distance layer: up to fuse_steps steps per
+  // launch, and one transform of the final maps
+  const SgKernel& kn = *E->step;
+  const int per_block = mcs::kEnvsPerBlock * kn.gpw;
   const int blocks = (E->s.B + per_block - 1) / per_block;
-  hipLaunchKernelGGL(k.fn, dim3(blocks), dim3(64 * mcs::kEnvsPerBlock), 0, st, E->s, dev_actions, dev_quot,
-                     dev_reward, dev_done);
-  SG_TRY(hipGetLastError());
+  const int64_t chunks = mc::fuse_chunk_count(num_steps, E->fuse_steps);
+  for (int64_t i = 0; i < chunks; ++i) {
+    mc::FuseChunk c;
+    if (!mc::fuse_chunk(num_steps, E->fuse_steps, i, stride, &c))
+      return sg_fail(MC_EINVAL, "mc_sg_step_many: chunk %lld of %lld", (long long)i, (long long)chunks);
+    mcs::SgLoopArgs a;
+    a.s = E->s;
+    a.actions = at(dev_actions, c.off[mc::FUSE_ACTIONS]);
+    a.quot = dev_quot ? at(dev_quot, c.off[mc::FUSE_OBS]) : nullptr;
+    a.reward = at(dev_reward, c.off[mc::FUSE_REWARD]);
+    a.done = at(dev_done, c.off[mc::FUSE_DONE]);
+    a.actions_stride = actions_stride;
+    a.quot_stride = quot_stride;
+    a.reward_stride = reward_stride;
+    a.done_stride = done_stride;
+    a.num_steps = c.count;
+    hipLaunchKernelGGL(kn.loop, dim3(blocks), dim3(64 * mcs::kEnvsPerBlock), 0, st, a);
+    const hipError_t he = hipGetLastError();
+    if (he != hipSuccess) {  // the launches before it are enqueued: the env has advanced c.first steps
+      E->stale = true;       // their maps have no transform yet: the next call runs it
+      return sg_fail(MC_EHIP,
+                     "mc_sg_step_many: step %lld of %d failed after %lld steps were enqueued: launch of %d steps: %s",
+                     (long long)c.first, (int)num_steps, (long long)c.first, (int)c.count, hipGetErrorString(he));
+    }
+    ++E->step_launches;
+    E->stale = true;
+  }
   SG_TRY(launch_dist(E, st));
   E->stale = false;
   return MC_OK;
+}
+
+int64_t mc_sg_launches(void* env, int32_t which) {
+  SgEnv* E = as_sg(env);
+  if (!E) return sg_fail(MC_EINVAL, "mc_sg_launches: null env");
+  if (which != 0 && which != 1) return sg_fail(MC_EINVAL, "mc_sg_launches: unknown counter %d", (int)which);
+  return which == 0 ? E->step_launches : E->dist_launches;
 }
 
 const char* mc_sg_kernel_variant(void* env) {

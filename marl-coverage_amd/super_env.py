@@ -200,6 +200,55 @@ class BatchSuperGridEnv:
         """Zero-overhead launch for benchmarks."""
         return self.lib.mc_sg_step(self._h, actions_ptr, None, reward_ptr, done_ptr, stream)
 
+    def rollout(self, actions, quot=None):
+        """Step K times with known actions in one C-ABI call (mc_sg_step_many):
+        ``actions`` uint8 [K, B, N] (as ``step``'s, per step), ``quot`` int32
+        [K, B] or None.  Returns ``((planes, dist), reward [K, B] float64,
+        done [K, B] uint8)``: step k's reward and done in new tensors, exactly
+        what K ``step`` calls would have returned (``self.reward`` /
+        ``self.done`` receive the last step's row), and the registered state
+        buffers holding the state after the last step -- the per-step state
+        planes are not returned.  Without ``dist_reward`` the steps run up to
+        MARLCOV_FUSE_STEPS (default 64) per kernel launch and the distance
+        layer is computed once, after the last step; with it every step is
+        launched as ``step`` launches it."""
+        torch = self._torch
+        a = actions
+        if not (isinstance(a, torch.Tensor) and a.dtype == torch.uint8 and a.device == self.device
+                and a.is_contiguous()):
+            a = torch.as_tensor(a, device=self.device).to(torch.uint8).contiguous()
+        if a.dim() != 3 or tuple(a.shape[1:]) != (self.num_envs, self.num_agents):
+            raise ValueError(f"actions must be [K, {self.num_envs}, {self.num_agents}] uint8")
+        K = a.shape[0]
+        q = None
+        if quot is not None:
+            q = torch.as_tensor(quot, device=self.device).to(torch.int32).contiguous()
+            if tuple(q.shape) != (K, self.num_envs):
+                raise ValueError(f"quot must be [{K}, {self.num_envs}] int32")
+        rew = torch.empty((K, self.num_envs), dtype=torch.float64, device=self.device)
+        done = torch.empty((K, self.num_envs), dtype=torch.uint8, device=self.device)
+        if K > 0:
+            _lib.check(self.lib.mc_sg_step_many(self._h, a.data_ptr(), a[0].numel(),
+                                                None if q is None else q.data_ptr(), self.num_envs * 4, K,
+                                                rew.data_ptr(), self.num_envs * 8, done.data_ptr(), self.num_envs,
+                                                self._stream()), "mc_sg_step_many")
+            self.reward.copy_(rew[-1])
+            self.done.copy_(done[-1])
+        return (self.planes, self.dist), rew, done
+
+    def step_many_raw(self, actions_ptr: int, actions_stride: int, num_steps: int, reward_ptr: int,
+                      done_ptr: int, stream: int):
+        """Benchmarks and tools: ``num_steps`` steps in one C call
+        (mc_sg_step_many), actions at ``actions_ptr + k * actions_stride``, no
+        quotients, every step's reward and done into the same buffers."""
+        return self.lib.mc_sg_step_many(self._h, actions_ptr, actions_stride, None, 0, num_steps, reward_ptr, 0,
+                                        done_ptr, 0, stream)
+
+    def launches(self):
+        """``(step, dist)``: the step-kernel and distance-kernel launches this
+        handle has issued (mc_sg_launches); a fused launch counts once."""
+        return int(self.lib.mc_sg_launches(self._h, 0)), int(self.lib.mc_sg_launches(self._h, 1))
+
     def field_shape(self, field):
         B, N, G, W, RW = self.num_envs, self.num_agents, self.num_grids, self.width, self.row_words
         return {
