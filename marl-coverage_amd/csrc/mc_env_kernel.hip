@@ -231,11 +231,11 @@ struct Ctx {
   static constexpr int RPW = RAYPROG ? ray_prog_row_words(RPL, SH::KM) : 4;  // words of a lane's program row
   static_assert(!RAYPROG || ray_prog_span(SH::N, (int)sizeof(WT), SH::KM) <= 32767, "ray program offsets are int16");
   // a step's lidar marks from the visibility table (mc_vistab.h; select_env:
-  // State::vis_tab is set) instead of the march: 8 lanes per agent land one
-  // record.  Only a reset's initial sense still marches (from its own program
-  // row, reset_env)
-  static constexpr bool VISTAB = RAYPROG && SH::VT != 0 && vis_fits(SH::H) && 8 * SH::N <= LPE;
-  uint32_t rp[RPW];  // RAYPROG: this lane's program row (round trip 1; VISTAB: a reset's only)
+  // State::vis_tab is set) instead of the march: every (agent, tile) item
+  // loads its own tile of its robot's record (vis_items), in a step and in a
+  // reset's initial sense alike -- such a kernel holds no march at all
+  static constexpr bool VISTAB = RAYPROG && SH::VT != 0 && vis_fits(SH::H);
+  uint32_t rp[RPW];  // RAYPROG without VISTAB: this lane's program row (round trip 1)
   int sub;    // lane within the env
   int lane;   // lane within the wave
   int lane0;  // first lane of this env's slot within the wave
@@ -453,8 +453,10 @@ __device__ __forceinline__ void stage_load(const State& s, const CT& C, int g, b
   // grid tiles first: the moves and the march need only them, so the mask
   // tiles (needed from the merge on) stay in flight meanwhile (loads return
   // in order; the compiler waits only for what each use needs)
+  // (a split visibility record holds the free and the obstacle marks apart:
+  // nothing reads the grid tiles then)
 #pragma unroll
-  for (int k = 0; k < KI; ++k) I.n[k] = ld_tile<O32>(s.grid_neg, gb + gt[k]);
+  for (int k = 0; k < KI; ++k) I.n[k] = (CT::VISTAB && kVisSplit) ? 0ull : ld_tile<O32>(s.grid_neg, gb + gt[k]);
   if (square) {
 #pragma unroll
     for (int k = 0; k < KI; ++k) I.p[k] = ld_tile<O32>(s.grid_pos, gb + gt[k]);
@@ -485,9 +487,7 @@ __device__ __forceinline__ uint64_t transpose8(uint64_t x) {
 
 // round trip 2, landing: the grid tiles into the row planes (and the tile
 // planes for the square sensor; the column planes for the fan march).
-// NEGR false: no grid row plane (a step whose marks come from the visibility
-// table: nothing reads it); the tiles outside the map still become obstacles
-template <class CT, bool NEGR = true, typename WT = typename CT::WT>
+template <class CT, typename WT = typename CT::WT>
 __device__ __forceinline__ void stage_scatter(const State& s, const CT& C, Items<CT::KI>& I) {
   constexpr int LPE = CT::LPE, KI = CT::KI;
   [[maybe_unused]] constexpr int EPW = CT::EPW;  // STAMP
@@ -518,10 +518,8 @@ __device__ __forceinline__ void stage_scatter(const State& s, const CT& C, Items
       const size_t off = (size_t)row_word<WT>(s, I.a[k], 8 * I.ti[k]) * sizeof(WT) + I.tj[k];
       const size_t rs = (size_t)row_step<WT>(s) * sizeof(WT);  // one window row
       const uint64_t ft = (known && I.masks && in) ? (I.f[k] | I.o[k]) : 0ull;
-      if constexpr (NEGR) {
 #pragma unroll
-        for (int r = 0; r < 8; ++r) nb[off + r * rs] = (uint8_t)(nt >> (8 * r));
-      }
+      for (int r = 0; r < 8; ++r) nb[off + r * rs] = (uint8_t)(nt >> (8 * r));
       if (known) {  // the cells the agent has seen (old free | obstacle tiles), the same way
 #pragma unroll
         for (int r = 0; r < 8; ++r) fb[off + r * rs] = (uint8_t)(ft >> (8 * r));
@@ -846,21 +844,22 @@ __device__ __forceinline__ void moves_front(const State& s, const CT& C, const F
 }
 
 // --------------------------------------------------------------------------
-// Visibility table (Ctx::VISTAB; mc_vistab.h): a step's lidar marks are the
-// record of the robot's post-move cell.  After the moves, lanes 8a .. 8a + 7
-// of the slot load 16 bytes each of the record of robot a's cell (vis_load)
-// and shift its rows into the mark-row plane (vis_land) -- where the march
-// would have left the same bits.  (MC_VIS_LATE 0, an A/B knob: a robot ends
-// its move on its own cell or on its target cell, both known after round trip
-// 1, so both records are loaded next to round trip 2 and one is selected
-// after the moves.)  Rows 4c .. 4c + 3 belong to lane 8a + c; a record has
-// 2H + 1 rows, so the lanes past the last row's quad reread that quad and
-// store nothing, like the lanes past 8N of a one-env workgroup.
+// Visibility table (Ctx::VISTAB; mc_vistab.h): the lidar's marks are the
+// record of the robot's cell, stored as map tiles.  Item (a, ti, tj) of a lane
+// is map tile (gi, gj); the record's origin tile is (ox, oy) = ((x - H) >> 3,
+// (y - H) >> 3), so the item's tile of the record is (gi - ox, gj - oy): one
+// 8-byte load per item (split form: two, the free and the obstacle marks),
+// straight into I.mf / I.mo -- no mark plane, no shift, no gather.  A step's
+// block origin comes from the pre-move cell and the robot moved at most one
+// cell, so ox - bx is 0 or 1: a tile of the block before the record's first
+// one takes 0, as does an item past `items`.  Addresses are clamped to the
+// table, whatever the positions hold.
 // --------------------------------------------------------------------------
-template <int NS>
-struct VisRec {
-  int4 own, tgt;  // this lane's quad of the records of the pre-move cell and of the target cell
-  uint32_t xy0;   // the pre-move cell of the lane's robot (Front::xy)
+template <int KI>
+struct VisTiles {
+  uint64_t m[KI];   // the item's mark tile (split form: its free-mark tile)
+  uint64_t mo[KI];  // split form: its obstacle-mark tile
+  bool on[KI];      // the item has a tile of the record
 };
 
 // pick() for the packed cells
@@ -875,69 +874,52 @@ __device__ __forceinline__ uint32_t pick_u(const uint32_t (&v)[NS], int a) {
   return r;
 }
 
-// MC_VIS_LATE 1 (default): one record load after the moves -- a dependent
-// round trip, but half the table traffic.  0 (A/B knob): both candidates'
-// records loaded next to round trip 2 and selected after the moves.  Measured
-// (profiles/r11/vistab/): 6.48-6.78 against 6.75-6.95 us at K = 200 and
-// 7.20-7.61 against 7.08-8.25 us at K = 20; the parent 7.73-7.76 / 8.12-8.39.
-#ifndef MC_VIS_LATE
-#define MC_VIS_LATE 1
-#endif
-
-// xy_after (MC_VIS_LATE): the robots' post-move cells -- that one record only
-template <class CT, int NS>
-__device__ __forceinline__ VisRec<NS> vis_load(const State& s, const CT& C, int g, const Front<NS>& F,
-                                               const uint32_t* xy_after = nullptr) {
-  constexpr int QL = (2 * CT::SH::H) / 4;  // the quad of the last row
-  const int av = min(C.sub >> 3, NS - 1), ch = min(C.sub & 7, QL);
-  VisRec<NS> V;
-  V.xy0 = pick_u<NS>(F.xy, av);
-  if (xy_after != nullptr) {
-    uint32_t xa[NS];
+// issue, after stage_load (I.gi / I.gj).  x[k], y[k]: the cell of item k's robot
+template <class CT>
+__device__ __forceinline__ VisTiles<CT::KI> vis_items_load(const State& s, const CT& C, int g, const Items<CT::KI>& I,
+                                                           const int (&x)[CT::KI], const int (&y)[CT::KI]) {
+  constexpr int KI = CT::KI, LPE = CT::LPE, H = CT::SH::H;
+  const int items = s.N * s.TW * s.TW;
+  const uint32_t last = (uint32_t)s.G * (uint32_t)s.Wp * (uint32_t)s.Lp - 1u;  // never past the table
+  VisTiles<KI> V;
 #pragma unroll
-    for (int i = 0; i < NS; ++i) xa[i] = xy_after[i];
-    V.xy0 = pick_u<NS>(xa, av);
-    const uint32_t last = (uint32_t)s.G * (uint32_t)s.Wp * (uint32_t)s.Lp - 1u;
-    const uint32_t i0 = min(vis_index(s.Wp, s.Lp, g, (int)(V.xy0 & 0xFFFFu), (int)(V.xy0 >> 16)), last);
-    V.own = V.tgt = *reinterpret_cast<const int4*>(reinterpret_cast<const char*>(s.vis_tab) + ch * 16 +
-                                                   (size_t)i0 * (kVisRecWords * 4));
-    return V;
+  for (int k = 0; k < KI; ++k) {
+    const uint32_t ri = (uint32_t)(I.gi[k] - ((x[k] - H) >> 3)), rj = (uint32_t)(I.gj[k] - ((y[k] - H) >> 3));
+    V.on[k] = (C.sub + k * LPE < items) & (ri < 4u) & (rj < 4u);
+    const uint32_t rec = min(vis_index(s.Wp, s.Lp, g, x[k], y[k]), last);
+    const char* p = reinterpret_cast<const char*>(s.vis_tab) + (size_t)rec * (kVisRecWords * 4) +
+                    (V.on[k] ? (ri * 4u + rj) * 8u : 0u);
+    V.m[k] = *reinterpret_cast<const uint64_t*>(p);
+    V.mo[k] = kVisSplit ? *reinterpret_cast<const uint64_t*>(p + kVisTiles * 8) : 0ull;
   }
-  const int act = pick<NS>(F.act, av);
-  const int x = (int)(V.xy0 & 0xFFFFu), y = (int)(V.xy0 >> 16);
-  const int tx = x + (act == 0) - (act == 2), ty = y + (act == 1) - (act == 3);
-  const bool inb = (unsigned)tx < (unsigned)s.Wp && (unsigned)ty < (unsigned)s.Lp;  // (else: blocked, the own cell again)
-  // never past the table, whatever the positions hold
-  const uint32_t last = (uint32_t)s.G * (uint32_t)s.Wp * (uint32_t)s.Lp - 1u;
-  const uint32_t i0 = min(vis_index(s.Wp, s.Lp, g, x, y), last);
-  const uint32_t i1 = min(vis_index(s.Wp, s.Lp, g, inb ? tx : x, inb ? ty : y), last);
-  const char* tab = reinterpret_cast<const char*>(s.vis_tab) + ch * 16;
-  V.own = *reinterpret_cast<const int4*>(tab + (size_t)i0 * (kVisRecWords * 4));
-  V.tgt = *reinterpret_cast<const int4*>(tab + (size_t)i1 * (kVisRecWords * 4));
   return V;
 }
 
-// xy_after: every robot's post-move cell (moves_front)
-template <class CT, int NS, typename WT = typename CT::WT>
-__device__ __forceinline__ void vis_land(const State& s, const CT& C, const Front<NS>& F, const VisRec<NS>& V,
-                                         const uint32_t (&xy_after)[NS]) {
-  static_assert(sizeof(WT) == 4, "a record row lands in a 32-bit window row");
-  constexpr int H = CT::SH::H, QL = (2 * H) / 4;
-  const int av = min(C.sub >> 3, NS - 1), ch = C.sub & 7;
-  const uint32_t xy = pick_u<NS>(xy_after, av);
-  const int4 r = xy == V.xy0 ? V.own : V.tgt;
-  // the record's row 0 / bit 0 in the agent's block: x - H - 8 bx in 0 .. 9,
-  // y - H - 8 by likewise (the block starts at most 7 cells before x0 - H - 1
-  // and the robot moved at most one cell): 21 + 9 bits fit the row
-  const int lx = (int)(xy & 0xFFFFu) - H - 8 * pick<NS>(F.bx, av) + 4 * ch;
-  const int sh = (int)(xy >> 16) - H - 8 * pick<NS>(F.by, av);
-  if (C.sub < 8 * NS && ch <= QL) {
-    WT* row = C.L.fpr + row_word<WT>(s, av, lx);
-    const int rs = row_step<WT>(s);
-    const uint32_t w[4] = {(uint32_t)r.x, (uint32_t)r.y, (uint32_t)r.z, (uint32_t)r.w};
+// landing: the marks into I.mf / I.mo, split by the staged grid tile (outside
+// the map: all obstacles, isInBounds) unless the record is; the free marks
+// also to LDS (other lanes' union dedup reads them)
+template <class CT>
+__device__ __forceinline__ void vis_items_land(const State& s, const CT& C, Items<CT::KI>& I,
+                                               const VisTiles<CT::KI>& V) {
+  constexpr int KI = CT::KI, LPE = CT::LPE;
+  const int items = s.N * s.TW * s.TW;
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (ch < QL || 4 * QL + j <= 2 * H) row[j * rs] = w[j] << sh;  // (the last quad: rows up to 2H only)
+  for (int k = 0; k < KI; ++k) {
+    const int idx = C.sub + k * LPE;
+    I.mf[k] = I.mo[k] = 0;
+    if (idx < items) {
+      const uint64_t m = V.on[k] ? V.m[k] : 0ull;
+      if constexpr (kVisSplit) {
+        I.mf[k] = m;
+        I.mo[k] = V.on[k] ? V.mo[k] : 0ull;
+      } else {
+        const uint64_t n = I.in[k] ? I.n[k] : ~0ull;
+        I.n[k] = n;
+        I.mf[k] = m & ~n;
+        I.mo[k] = m & n;
+      }
+      C.L.fp[idx] = I.mf[k];
+    }
   }
 }
 
@@ -1018,9 +1000,10 @@ __device__ __forceinline__ void load_ray_prog(const State& s, CT& C) {
   }
 }
 // C with its program row loaded anew (a copy); C itself without programs
+// (VISTAB: no march, so no program)
 template <class CT>
 __device__ __forceinline__ decltype(auto) with_ray_prog(const State& s, const CT& C) {
-  if constexpr (CT::RAYPROG) {
+  if constexpr (CT::RAYPROG && !CT::VISTAB) {
     CT c = C;
     load_ray_prog(s, c);
     return c;
@@ -1829,7 +1812,8 @@ __device__ __forceinline__ void sentinel_done(const State& s, const EnvIO& io, i
 }
 
 // sense -> (lidar: gather) -> (single tool) -> merge, with the barriers.
-// MARKED: the mark rows are written already (vis_land): no march
+// MARKED: the items hold their mark tiles already (vis_items_land): no march,
+// no gather
 template <class CT, bool MARKED = false>
 __device__ __forceinline__ void sense_and_merge(const State& s0, const CT& C, Items<CT::KI>& I) {
   [[maybe_unused]] constexpr int EPW = CT::EPW;  // STAMP
@@ -1839,9 +1823,11 @@ __device__ __forceinline__ void sense_and_merge(const State& s0, const CT& C, It
   }
   __syncthreads();
   STAMP(13);
-  if (s.sensor == 0) {
-    gather_marks(s, C, I);
-    __syncthreads();
+  if constexpr (!MARKED) {
+    if (s.sensor == 0) {
+      gather_marks(s, C, I);
+      __syncthreads();
+    }
   }
   STAMP(4);
   if (s.sst) {
@@ -1870,7 +1856,8 @@ __device__ __forceinline__ void reset_env(const State& s, const CT& C0, const in
   constexpr int LPE = CT::LPE, KI = CT::KI;
   // RAYPROG: the lane's program row again, for the initial sense (lands
   // during the zeroing below) -- the step's copy then dies with its march
-  // instead of staying in registers up to here
+  // instead of staying in registers up to here.  (VISTAB: the initial sense
+  // reads the table like a step's)
   const auto& C = with_ray_prog(s, C0);
   const Lds<WT>& L = C.L;
   const int N = s.N;
@@ -1909,7 +1896,7 @@ __device__ __forceinline__ void reset_env(const State& s, const CT& C0, const in
         bad |= (inj_pos[((size_t)e * N + j) * 2] == x && inj_pos[((size_t)e * N + j) * 2 + 1] == y);
       if (bad) atomicOr(s.err, ERR_INJECT);
       set_agent<WT>(s, L, C.sub, x, y);
-      if constexpr (CT::RAYPROG)
+      if constexpr (CT::RAYPROG && !CT::VISTAB)
         ray_p0_words(L)[C.sub] = ray_p0(s, L, C.sub, x, y, (x - s.H - 1) >> 3, (y - s.H - 1) >> 3);
     }
   } else if (C.sub < 64) {
@@ -1939,7 +1926,7 @@ __device__ __forceinline__ void reset_env(const State& s, const CT& C0, const in
     if (placed < N && lane == 0) atomicOr(s.err, ERR_PLACEMENT);
     if (lane < N) {
       set_agent<WT>(s, L, lane, px, py);
-      if constexpr (CT::RAYPROG)
+      if constexpr (CT::RAYPROG && !CT::VISTAB)
         ray_p0_words(L)[lane] = ray_p0(s, L, lane, px, py, (px - s.H - 1) >> 3, (py - s.H - 1) >> 3);
     }
   }
@@ -1947,10 +1934,24 @@ __device__ __forceinline__ void reset_env(const State& s, const CT& C0, const in
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   Items<KI> I;
-  zero_marks(s, C);
-  stage(s, C, g, /*load_masks=*/false, I);
-  __syncthreads();
-  sense_and_merge(s, C, I);
+  if constexpr (CT::VISTAB) {
+    // the robots' cells are in L.x / L.y; the maps are known zero
+    stage_load(s, C, g, /*load_masks=*/false, I);
+    int xk[KI], yk[KI];
+#pragma unroll
+    for (int k = 0; k < KI; ++k) {
+      xk[k] = L.x[I.a[k]];
+      yk[k] = L.y[I.a[k]];
+    }
+    const VisTiles<KI> V = vis_items_load(s, C, g, I, xk, yk);
+    vis_items_land(s, C, I, V);
+    sense_and_merge<CT, true>(s, C, I);
+  } else {
+    zero_marks(s, C);
+    stage(s, C, g, /*load_masks=*/false, I);
+    __syncthreads();
+    sense_and_merge(s, C, I);
+  }
   store_tiles(s, C, I);
   __syncthreads();
   if (C.sub == 0) {
@@ -2241,7 +2242,7 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
   const bool lidar = s.sensor == 0;
   const int nbl = lidar ? s.nbeams : 1;  // a square env reads a dummy record
   // (RAYPROG: the lane's ray program row instead of a beam record)
-  // (VISTAB: a step does not march; reset_env loads the row for itself)
+  // (VISTAB: neither a step nor a reset marches)
   if constexpr (CT::RAYPROG && !CT::VISTAB) load_ray_prog(s, C);
   const int4 bm0 = CT::RAYPROG ? make_int4(0, 0, 0, 0)
                                : reinterpret_cast<const int4*>(lidar ? (const void*)s.beams : (const void*)s.pos)
@@ -2266,7 +2267,7 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
     chd = hp[0];
     chb = *reinterpret_cast<const int2*>(hp + 1);
   }
-  zero_marks(s, C);  // overlaps the round trip
+  if constexpr (!CT::VISTAB) zero_marks(s, C);  // overlaps the round trip (VISTAB: no mark plane)
   // every result is needed below: keep the compiler from sinking a load into
   // the branch that uses it (that would make it a round trip of its own)
   asm volatile("" ::"v"(p0.x), "v"(p0.y), "v"(act_raw), "v"(act0_raw), "v"(req_raw), "v"(g0),
@@ -2329,6 +2330,7 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
   if (active) {
     STAMP(1);
     Items<KI> I;
+    [[maybe_unused]] VisTiles<KI> V;  // VISTAB: the items' tiles of their robots' records, in flight
     if constexpr (FRONT) {
       // ---- round trip 2, issue: the robots' target-cell grid tiles first
       // (the moves wait only for them), then every staged tile; block
@@ -2341,18 +2343,21 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
       const uint64_t tt = ld_tile<O32>(s.grid_neg, __umul24((uint32_t)g0, (uint32_t)s.MT) +
                                                        tile_index24(s.TCS, inb ? tx >> 3 : 0, inb ? ty >> 3 : 0));
       if constexpr (CT::VISTAB) {
-        // ... and both candidate records of every robot, before the staged
-        // tiles (loads return in order: the mask tiles stay in flight past
-        // the landing)
-        VisRec<NSM> V;
-        if constexpr (!MC_VIS_LATE) V = vis_load(s, C, g0, F);
+        // ... and after the moves every item's tile of the record of its
+        // robot's post-move cell: a dependent round trip, landed before the
+        // merge (vis_items_land).  No row plane is scattered: nothing marches
         stage_load(s, C, g0, true, I, &F);
         uint32_t xy_after[NSM];
         moves_front(s, C, F, !inb || ((tt >> tile_bit(tx, ty)) & 1ull), (uint32_t)tx | ((uint32_t)ty << 16), act,
                     moved0, -s.pen, xy_after);
-        if constexpr (MC_VIS_LATE) V = vis_load(s, C, g0, F, xy_after);
-        vis_land(s, C, F, V, xy_after);
-        stage_scatter<CT, false>(s, C, I);
+        int xk[KI], yk[KI];
+#pragma unroll
+        for (int k = 0; k < KI; ++k) {
+          const uint32_t xy = pick_u<NSM>(xy_after, I.a[k]);
+          xk[k] = (int)(xy & 0xFFFFu);
+          yk[k] = (int)(xy >> 16);
+        }
+        V = vis_items_load(s, C, g0, I, xk, yk);
       } else {
         stage_load(s, C, g0, true, I, &F);
         moves_front(s, C, F, !inb || ((tt >> tile_bit(tx, ty)) & 1ull), (uint32_t)tx | ((uint32_t)ty << 16), act,
@@ -2431,6 +2436,7 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
       dpre0 = pr[0];
       dprek = pr[1 + k];
     }
+    if constexpr (CT::VISTAB) vis_items_land(s, C, I, V);
     sense_and_merge<CT, CT::VISTAB>(s, C, I);
     __syncthreads();
     STAMP(5);

@@ -198,7 +198,7 @@ struct State {
   // ray_prog_row_words words per lane of an env slot
   const uint32_t* ray_prog;
   // The lidar's visibility table (mc_vistab.h; null: none, the kernels march):
-  // one 128-byte record of mark rows per (pool grid, cell), rebuilt whenever
+  // one 128-byte record of mark tiles per (pool grid, cell), rebuilt whenever
   // the pool or the beam table changes
   const uint32_t* vis_tab;
 };

@@ -19,7 +19,13 @@
 namespace mc {
 
 constexpr int kVisRows = 21;      // rows (and bits per row) a record can hold: H <= 10
-constexpr int kVisRecWords = 32;  // u32 words per record: one 128-byte line
+// the record's form.  Unsplit is the measured choice (profiles/r14/vis_tiles/)
+#ifndef MC_VIS_SPLIT
+#define MC_VIS_SPLIT 0
+#endif
+constexpr bool kVisSplit = MC_VIS_SPLIT != 0;
+constexpr int kVisTiles = 16;                          // tiles of one plane of a record: 4 x 4
+constexpr int kVisRecWords = kVisSplit ? 64 : 32;      // u32 words per record: one or two 128-byte lines
 
 // whether a State's lidar fits a record
 __host__ __device__ constexpr bool vis_fits(int H) { return H >= 1 && 2 * H + 1 <= kVisRows; }
@@ -76,6 +82,39 @@ __host__ __device__ inline void vis_record(const uint64_t* neg, int TCS, int Wp,
       if (vis_blocked(neg, TCS, Wp, Lp, cx, cy)) break;  // oc[int(cx), int(cy)] < 0: the beam ends here
     }
   }
+}
+
+// The table's record of cell (x, y) from vis_record's rows: the marks as map
+// tiles (see the head of this file).  SPLIT: 16 free-mark tiles, then 16
+// obstacle-mark tiles -- a mark is an obstacle mark where vis_blocked, which
+// for whole tiles is the grid tile itself (cells of an edge tile beyond the map
+// are set in it: pack_grids_kernel) or all ones outside the map's tiles.
+// out: 16 (SPLIT: 32) tiles, all written.
+template <bool SPLIT>
+__host__ __device__ inline void vis_tiles_as(const uint32_t* rows, const uint64_t* neg, int TCS, int Wp, int Lp, int H,
+                                             int x, int y, uint64_t* out) {
+  const int ox = (x - H) >> 3, oy = (y - H) >> 3;  // arithmetic shifts: floor
+  const int rx = (x - H) - 8 * ox, ry = (y - H) - 8 * oy;  // 0 .. 7
+  for (int t = 0; t < (SPLIT ? 2 : 1) * kVisTiles; ++t) out[t] = 0ull;
+  for (int r = 0; r <= 2 * H; ++r) {
+    const uint32_t w = rows[r] << ry;  // the window row from its first tile's column 0: 7 + 21 bits
+    const int lx = rx + r;
+    for (int j = 0; j < 4; ++j) out[4 * (lx >> 3) + j] |= (uint64_t)((w >> (8 * j)) & 0xFFu) << (8 * (lx & 7));
+  }
+  if (SPLIT) {
+    const int TR = (Wp + 7) >> 3, TC = (Lp + 7) >> 3;
+    for (int t = 0; t < kVisTiles; ++t) {
+      const int gi = ox + (t >> 2), gj = oy + (t & 3);
+      const uint64_t n = (gi >= 0 && gj >= 0 && gi < TR && gj < TC) ? neg[tile_index(TCS, gi, gj)] : ~0ull;
+      const uint64_t m = out[t];
+      out[t] = m & ~n;
+      out[kVisTiles + t] = m & n;
+    }
+  }
+}
+__host__ __device__ inline void vis_tiles(const uint32_t* rows, const uint64_t* neg, int TCS, int Wp, int Lp, int H,
+                                          int x, int y, uint64_t* out) {
+  vis_tiles_as<kVisSplit>(rows, neg, TCS, Wp, Lp, H, x, y, out);
 }
 
 // the build kernel's launcher (mc_vistab.hip): every record of the pool's
