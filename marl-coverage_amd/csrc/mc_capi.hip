@@ -15,6 +15,7 @@
 
 #include "marlcov.h"
 #include "mc_internal.h"
+#include "mc_env_select.h"
 #include "mc_fork.h"
 #include "mc_fuse.h"
 #include "mc_vistab.h"
@@ -24,7 +25,6 @@ hipError_t launch_env(const State& s, int mode, const uint8_t* actions, const ui
                       const int32_t* inj_pos, double* reward, uint8_t* done, uint8_t* obs,
                       uint8_t* adj, int num_steps, const EnvStrides& strides, int nt, int epw,
                       hipStream_t stream);
-int env_pack(const State& s);
 hipError_t launch_share(const State& s, const uint8_t* actions, hipStream_t stream);
 hipError_t launch_rec_field(const State& s, int off, int width, void* buf, bool to_rec, hipStream_t stream);
 hipError_t launch_pack(const State& s, const int8_t* grids, hipStream_t stream);
@@ -172,18 +172,6 @@ int dev_alloc(Env* E, void** p, size_t bytes) {
   return MC_OK;
 }
 
-int env_threads(const mc::State& s) {
-  // every lane stages at most kMaxItemsPerLane (agent, tile) items; beyond
-  // that, prefer one wave per env (no cross-wave barriers) unless the beam
-  // march would need more than ~8 sequential rounds per lane
-  const int items = s.N * s.TW * s.TW;
-  int nt = 64;
-  while (nt < 1024 && items > mc::kMaxItemsPerLane * nt) nt *= 2;
-  if (s.sensor == MC_SENSOR_LIDAR)
-    while (nt < 256 && s.N * s.nbeams > 8 * nt) nt *= 2;
-  return nt;
-}
-
 Env* as_env(void* p) { return static_cast<Env*>(p); }
 
 int launch_epw(const Env* E);
@@ -219,13 +207,10 @@ int vis_refresh(Env* E, hipStream_t st, const char* who) {
 // lanes per env workgroup and envs per workgroup for the current state
 // (mc_create, and again when mc_set_beam_table changes the beam count)
 void set_launch_shape(Env* E) {
-  E->nt = env_threads(E->s);
-  if (const char* ov = getenv("MARLCOV_NT")) {  // tuning / test override (64..1024)
-    const int v = atoi(ov);
-    if (v == 64 || v == 128 || v == 256 || v == 512 || v == 1024) E->nt = v > E->nt ? v : E->nt;
-  }
-  E->epw = mc::env_pack(E->s);
-  if (E->nt > 64) E->epw = 1;  // (only the MARLCOV_NT override gets here with a packable env)
+  const char* ov = getenv("MARLCOV_NT");  // tuning / test override (64..1024)
+  const mc::EnvGeom g = mc::env_geometry(E->s, ov ? atoi(ov) : 0);
+  E->nt = g.nt;
+  E->epw = g.epw;
 }
 
 // envs per workgroup for this launch; MARLCOV_EPW=1 forces one env per
@@ -597,7 +582,7 @@ int mc_query(void* env, mc_layout* out) {
   return MC_OK;
 }
 
-// Fan march data of a dense beam set (mc_env_kernel.hip fan_march, layout in
+// Fan march data of a dense beam set (mc_env_step.h fan_march, layout in
 // mc_internal.h State::fan_data).  Beams are grouped by octant class (major
 // axis, major sign, minor sign; minor sign 0 counts as +), ordered by their
 // minor offsets, and cut greedily into sectors of up to kFanS beams whose

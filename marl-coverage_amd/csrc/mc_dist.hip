@@ -775,7 +775,7 @@ __device__ uint64_t strip_run_mask(const State& s, int pad, uint32_t ea, int the
 }
 
 // The State re-read from the kernel arguments at the item's phase boundaries
-// (as the env kernel's reload_state, mc_env_kernel.hip): the fields a phase
+// (as the env kernel's reload_state, mc_env_step.h): the fields a phase
 // uses are loaded there instead of living in SGPRs -- spilled to VGPR lanes,
 // a VALU v_readlane per use -- across the item loop
 struct DistIO {
@@ -1957,7 +1957,7 @@ hipError_t launch_dist(const State& s, int pad, int post, float* pre_out, float*
 // with d == M (then d(witness) is still M, and no cell exceeds M).  The
 // targets (the E x E crop and the 5 end cells of the next step) are near the
 // robot, so the env kernel settles their d from the agent's staged block
-// (mc_env_kernel.hip dist_window) and lists only the maps with an unknown M
+// (mc_env_step.h dist_window) and lists only the maps with an unknown M
 // or a target the block cannot settle.  With the top-cell cache, the listed
 // maps first try the cache (mode 1) and the rest run split over workgroups
 // (mode 2; `full`: the full list), the part that finishes last finalising

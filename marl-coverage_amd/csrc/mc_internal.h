@@ -117,7 +117,7 @@ struct State {
   // the robot (bit 3*(dx+1) + (dy+1)); the march marks them once per agent
   // instead of once per ray (0 = no premark, the march marks step 1)
   uint32_t beam_k1;
-  // Fan march of a dense beam set (mc_env_kernel.hip fan_march; built by
+  // Fan march of a dense beam set (mc_env_step.h fan_march; built by
   // mc_set_beam_table, off when fan_nsec + fan_nspec == 0).  fan_data: the
   // spread / expand LUTs (kFanLutBytes), fan_nsec / 2 sector-pair records of
   // 2 (fan_kt + 1) words (the two sectors of one line, interleaved: words 0, 1
@@ -140,7 +140,7 @@ struct State {
   // sets M = -1 when sensing covers a cell closer than M to the witness (or
   // the env resets); otherwise M is unchanged (mc_dist.hip).
   int32_t* dist_mw;
-  // dist_reward POST outputs of the env kernel's window search (mc_env_kernel
+  // dist_reward POST outputs of the env kernel's window search (mc_env_step.h
   // dist_window): the caller's float32 obs layer [B][N][E][E] and the header
   // of the full transform's work list (count at [0], entries from [5]:
   // mc_dist.hip dist_kernel_t)
@@ -267,7 +267,7 @@ __host__ __device__ constexpr uint32_t magic_div(uint32_t d) {
   return d <= 1 ? 0u : (uint32_t)((0x100000000ull + d - 1) / d);
 }
 
-// Words of one row plane of the env kernel (mc_env_kernel.hip row_word):
+// Words of one row plane of the env kernel (mc_env_step.h row_word):
 // 32-bit rows are agent-interleaved with an odd stride N | 1 (row lx of agent
 // a is word lx * (N | 1) + a), 64-bit rows agent-major, 8*TW + 1 apart.
 __host__ __device__ inline int row_plane_words(int N, int TW, int rowbytes) {
@@ -277,7 +277,7 @@ __host__ __device__ inline int row_plane_words(int N, int TW, int rowbytes) {
 // words between two window rows of one agent in a row plane (row_word)
 __host__ __device__ constexpr int row_step_words(int N, int rowbytes) { return rowbytes == 4 ? (N | 1) : 1; }
 
-// Ray march geometry (mc_env_kernel.hip sense), shared by the kernel's Ctx
+// Ray march geometry (mc_env_step.h sense), shared by the kernel's Ctx
 // and the host's ray programs: an env slot has nt / epw lanes; a lane takes
 // ray_rpl rays per pass -- 2 with one env per workgroup, 3 with two (C4 A/B:
 // 3, 4 or 6 per lane are slower), and 3 for a compiled sparse-beam shape of
@@ -302,7 +302,7 @@ __host__ __device__ constexpr int ray_rpl(int nt, int epw, int n, int nb) {
 // its agent's cell).  Lane `sub` of a slot marches rays idx = sub * rpl + j
 // (j < rpl) of agent idx / nbeams, beam idx % nbeams.  Its row: rpl * km
 // int16 offsets T[j * km + k - 1] (k = 1 .. km), two per word, low half
-// first -- the ray's packed cell (mc_env_kernel.hip struct Ray) at step k is
+// first -- the ray's packed cell (mc_env_step.h struct Ray) at step k is
 // P0(agent) + T; then zero padding to whole 16-byte quads less one word; the
 // last word holds a byte per ray: bits 0-4 K + 1 (0: idx >= N * nbeams, a
 // dead ray), bits 5-7 the agent.  The table is stored by 16-byte quads, quad
@@ -357,7 +357,7 @@ inline bool build_ray_prog(const std::vector<Beam>& bt, int N, int lpe, int rpl,
   return true;
 }
 
-// Fan march (mc_env_kernel.hip fan_march): sectors of up to kFanS adjacent
+// Fan march (mc_env_step.h fan_march): sectors of up to kFanS adjacent
 // beams of one octant class march together.  Entry of step k (u32):
 // bits 0-5 lo + 32 (signed minor offset of the sector's first cell), bits 6-10
 // D (bit j: beam j+1 sits one cell past beam j), bits 16-21 the beams still in
@@ -374,7 +374,7 @@ enum : uint32_t { FAN_COLS = 1u, FAN_NEG = 2u, FAN_SPECIAL = 4u };
 
 // LDS bytes of the fan region (replaces the beam records): the fan data and
 // the per-(agent, special beam) pair records.  The fan's column planes share
-// the tile region (env_lds_bytes; mc_env_kernel.hip carve).
+// the tile region (env_lds_bytes; mc_env_step.h carve).
 __host__ __device__ inline size_t fan_lds_bytes(int N, int nspec, int kt, int words) {
   return (size_t)words * 4 + (size_t)N * nspec * 2 * (kt + 1) * 4;
 }
@@ -413,34 +413,47 @@ __host__ __device__ inline size_t slot_stride(size_t slot_lds) {
 // Compile-time shape of an env kernel instantiation: fields > 0 are baked in
 // (loop bounds, divisions and LDS offsets fold to constants and the march
 // unrolls); 0 leaves the field to the runtime State.  The launcher picks a
-// specialised instantiation only when the runtime State matches it exactly.
-// LC: obs layers of an EGO shape (3; 4 with dijkstra_input, whose layer 3 the
-// dijkstra kernel writes after the env kernel, or with dist_reward, whose
-// layer 3 is the float buffer: 0 in the uint8 obs).  DS: an EGO shape's
-// dist_reward flag (baked in).  FN / FS / FW: a dense-beam shape's fan
-// march -- sector slots, special beams and fan words (mc_set_beam_table's
-// build_fan; its trip count is KM): the fan's LDS offsets (carve) then fold
-// to constants instead of living in SGPRs across the kernel.  BW: a bench
-// instantiation -- square padded grids of side BW (the tile geometry and the
-// beam-bit row length fold to constants) with the bench's episode flags (no
-// comm graph, grids kept on reset, auto-reset on).  VT: the step reads its
-// lidar marks from the visibility table (State::vis_tab, set: select_env)
-// instead of marching.
-template <int N_, int H_, int NB_, int EGO_, int KM_, int KN_ = 0, int LC_ = 3, int DS_ = 0, int FN_ = 0,
-          int FS_ = 0, int FW_ = 0, int BW_ = 0, int VT_ = 0>
-struct Shape {
-  static constexpr int N = N_, H = H_, NB = NB_, EGO = EGO_, KM = KM_, KN = KN_, LC = LC_, DS = DS_;
-  static constexpr int FN = FN_, FS = FS_, FW = FW_, BW = BW_, VT = VT_;
-  __host__ __device__ static bool matches(const State& s) {
-    return (N_ == 0 || s.N == N_) && (H_ == 0 || s.H == H_) &&
-           (NB_ == 0 || (s.sensor == 0 && s.nbeams == NB_)) &&
-           (EGO_ == 0 || (s.ego == EGO_ && s.Lc == LC_ && (s.dist != 0) == (DS_ != 0))) &&
-           (KM_ == 0 || (s.sensor == 0 && s.beam_kmax == KM_)) &&
-           (KN_ == 0 || (s.sensor == 0 && s.beam_kmin == KN_)) &&
-           (FN_ == 0 || (s.fan_nsec == FN_ && s.fan_nspec == FS_ && s.fan_words == FW_ && s.fan_kt == KM_)) &&
-           (BW_ == 0 || (s.Wp == BW_ && s.Lp == BW_ && s.comm_r == 0 && s.grid_mode == 0 && s.auto_reset == 1));
-  }
+// specialised instantiation only when the runtime State matches it exactly
+// (shape_matches).  A shape is a struct that derives from ShapeNone, or from
+// another shape, and redeclares the fields in which it differs
+// (mc_env_select.h has the compiled ones).
+struct ShapeNone {
+  static constexpr int N = 0;    // agents
+  static constexpr int H = 0;    // sensing half-width
+  static constexpr int NB = 0;   // lidar beams
+  static constexpr int EGO = 0;  // egoradius
+  static constexpr int KM = 0;   // beam_kmax (a fan's trip count)
+  static constexpr int KN = 0;   // beam_kmin
+  // obs layers of an EGO shape (3; 4 with dijkstra_input, whose layer 3 the
+  // dijkstra kernel writes after the env kernel, or with dist_reward, whose
+  // layer 3 is the float buffer: 0 in the uint8 obs)
+  static constexpr int LC = 3;
+  static constexpr int DS = 0;  // an EGO shape's dist_reward flag (baked in)
+  // a dense-beam shape's fan march -- sector slots, special beams and fan
+  // words (mc_set_beam_table's build_fan; its trip count is KM): the fan's LDS
+  // offsets (carve) then fold to constants instead of living in SGPRs across
+  // the kernel
+  static constexpr int FN = 0, FS = 0, FW = 0;
+  // a bench instantiation -- square padded grids of side BW (the tile geometry
+  // and the beam-bit row length fold to constants) with the bench's episode
+  // flags (no comm graph, grids kept on reset, auto-reset on)
+  static constexpr int BW = 0;
+  // the step reads its lidar marks from the visibility table (State::vis_tab,
+  // set: select_env_row) instead of marching
+  static constexpr int VT = 0;
 };
+using Dynamic = ShapeNone;  // nothing baked in: the generic kernels
+
+template <class SH>
+inline bool shape_matches(const State& s) {
+  return (SH::N == 0 || s.N == SH::N) && (SH::H == 0 || s.H == SH::H) &&
+         (SH::NB == 0 || (s.sensor == 0 && s.nbeams == SH::NB)) &&
+         (SH::EGO == 0 || (s.ego == SH::EGO && s.Lc == SH::LC && (s.dist != 0) == (SH::DS != 0))) &&
+         (SH::KM == 0 || (s.sensor == 0 && s.beam_kmax == SH::KM)) &&
+         (SH::KN == 0 || (s.sensor == 0 && s.beam_kmin == SH::KN)) &&
+         (SH::FN == 0 || (s.fan_nsec == SH::FN && s.fan_nspec == SH::FS && s.fan_words == SH::FW && s.fan_kt == SH::KM)) &&
+         (SH::BW == 0 || (s.Wp == SH::BW && s.Lp == SH::BW && s.comm_r == 0 && s.grid_mode == 0 && s.auto_reset == 1));
+}
 
 // overwrite the baked-in fields of a kernel's State copy with constants
 template <class SH>

@@ -46,7 +46,7 @@ __host__ __device__ inline bool vis_blocked(const uint64_t* neg, int TCS, int Wp
   return (neg[tile_index(TCS, x >> 3, y >> 3)] >> (((x & 7) << 3) | (y & 7))) & 1ull;
 }
 
-// The record of cell (x, y): the generic march of mc_env_kernel.hip (ray_init,
+// The record of cell (x, y): the generic march of mc_env_step.h (ray_init,
 // ray_advance, ray_mark and sense()'s premarks) run for every beam from that
 // cell.  beam_bits / bcmax / beam_common / beam_k1 as in State.  rec:
 // kVisRecWords words, all written.

@@ -9,7 +9,7 @@ host bit for bit, so a caller can know without a device round trip which grid
 
     philox4x32_10        csrc/mc_device.h philox()
     generated_grid       csrc/mc_grid_kernels.hip gen_grids_kernel
-    start_cells          csrc/mc_env_kernel.hip reset_env (rejection draw,
+    start_cells          csrc/mc_env_step.h reset_env (rejection draw,
                          acceptance rule of dec_grid_rl.py:491-502)
     random_actions       csrc/mc_grid_kernels.hip random_actions_kernel
 """

@@ -5,7 +5,7 @@
 // Input (a text file): per case one line "N lpe rpl km rowbytes nbeams", then
 // per beam "K axis sign msign bits".  For every lane, ray and step the
 // program's offset must equal a direct replay of the march's chain
-// (mc_env_kernel.hip ray_init / ray_advance), fit int16, and the ray's K and
+// (mc_env_step.h ray_init / ray_advance), fit int16, and the ray's K and
 // agent must be the mapping's (K = -1 for rays past N * nbeams).
 #include <cstdint>
 #include <cstdio>

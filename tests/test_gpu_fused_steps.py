@@ -1,4 +1,4 @@
-"""GPU: mc_step_many's fused launches (mc_env_kernel.hip: io.num_steps steps
+"""GPU: mc_step_many's fused launches (mc_env_step.h: io.num_steps steps
 inside one env-kernel launch; mc_capi.hip / mc_fuse.h: ceil(K / S) launches,
 S = MARLCOV_FUSE_STEPS read at mc_create).  Every case builds two identical
 envs, drives one by ``rollout`` (fused) and the other by K ``step`` calls, and

@@ -3,14 +3,12 @@ waves (env_kernel<512 / 1024, 1, u32 / u64, generic>), which only configs with
 many robots and a wide window select, and the square sensor beyond the one
 shape the other suites run (<64, 2, u32>).
 
-mc_create picks the shape (csrc/mc_capi.hip env_threads, csrc/mc_env_kernel.hip
-env_pack / select_env): with H = max(ceil(range), egoradius) the window has
-TW = (2 H + 17) // 8 tiles per side and the env stages N * TW^2 (agent, tile)
-items, at most kMaxItemsPerLane = 2 per lane: 64 lanes up to 128 items, 128 up
-to 256, 256 up to 512, 512 up to 1,024, 1,024 up to the accepted 2,048 (the
-lidar also takes 128 / 256 lanes when N * beams > 512 / 1,024).  Two envs share
-a wave when N <= 32, items <= 64 and N * beams <= 96.  Rows are u32 for
-TW <= 4, else u64.  The LDS slot (csrc/mc_internal.h env_lds_bytes), with
+mc_create picks the shape (csrc/mc_env_select.h env_geometry = env_threads,
+env_pack and the MARLCOV_NT rule, then select_env_row) from N, the window's
+TW = (2 H + 17) // 8 tiles per side (H = max(ceil(range), egoradius)), the
+beam count and the sensor; tests/native/env_select_check.cpp checks those
+rules on the host for every config of the ORGANIC table below.  Rows are u32
+for TW <= 4, else u64.  The LDS slot (csrc/mc_internal.h env_lds_bytes), with
 rb = 4 (u32) or 8 and P = 8 TW (N | 1) (u32) or N (8 TW + 1) row-plane words:
 
     (3 lidar | 6 square) * N * TW^2 * 8  +  pad16(3 P rb)  +  16 * max(beams, 1)

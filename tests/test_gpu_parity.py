@@ -137,7 +137,7 @@ BATCH_CASES = {
                          lambda rs: bern(rs, 40, 40, 0.1), 2, 12),
     "limit_range27_ego15": (base_cfg(numrobot=4, egoradius=15, sensor_config={"num_lasers": 13, "range": 27}),
                             lambda rs: bern(rs, 90, 70, 0.1), 2, 10),
-    # dense beam sets: the fan march (sectors of adjacent beams, mc_env_kernel
+    # dense beam sets: the fan march (sectors of adjacent beams, mc_env_step.h
     # fan_march) on 64-bit rows with special beams, without special beams at
     # range 27, and on 32-bit rows (window of 3 x 3 tiles)
     "fan_128beams_r13_nonsquare": (base_cfg(numrobot=3, allow_even_beams=True,
@@ -572,7 +572,7 @@ def test_batch_dist_multi_wave_slot(torch_cuda, name, monkeypatch):
 def test_batch_dist_packed_slots(torch_cuda):
     """dist_reward configs whose envs pack two to a wave (env_kernel<64,2,...>):
     each env slot of the wave appends its listed maps to its own env's shard
-    of the full-transform work list (csrc/mc_env_kernel.hip, the slot-masked
+    of the full-transform work list (csrc/mc_env_step.h, the slot-masked
     ballot) -- the oracle comparison of every step covers the transform of
     those entries (dec_grid_rl.py:222-223,239-240,260-282)."""
     import marlcov

@@ -1,5 +1,5 @@
 """GPU: the sparse-beam march from host-built ray programs (csrc/
-mc_internal.h build_ray_prog, mc_env_kernel.hip Ctx::RAYPROG): the compiled C2
+mc_internal.h build_ray_prog, mc_env_select.h EnvCfg::RAYPROG): the compiled C2
 / C2D instantiations read each ray's cell as the agent's packed cell plus a
 precomputed 16-bit offset.  Every case steps against the oracle (oracle/
 cpu_ref.py) and compares reward (tolerance 0), done, obs, positions, maps and

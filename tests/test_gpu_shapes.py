@@ -1,7 +1,7 @@
 """GPU parity of the compiled-shape kernels the benchmark times.
 
 The env kernel is instantiated per BASELINE workload shape (csrc/
-mc_env_kernel.hip select_env: C2, C2D = C2 + dijkstra_input, C4, C5); every
+mc_env_select.h MC_ENV_ROWS: C2, C2D = C2 + dijkstra_input, C4, C5); every
 other config runs the generic instantiation.  These tests run each compiled
 shape — asserted through mc_kernel_variant — against the oracle
 (oracle/cpu_ref.py) every step, including the auto-reset branch inside the

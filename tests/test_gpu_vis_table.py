@@ -1,5 +1,5 @@
 """GPU: the lidar's marks read from the per-grid visibility table (csrc/
-mc_vistab.h, mc_env_kernel.hip Ctx::VISTAB) instead of marched.  Every case
+mc_vistab.h, mc_env_select.h EnvCfg::VISTAB) instead of marched.  Every case
 steps against the oracle (oracle/cpu_ref.py) and compares reward (tolerance
 0), done, obs, positions, maps and counters every step, once under
 MARLCOV_VIS_TABLE=require (a handle without a table is an error, so the table

@@ -1,5 +1,5 @@
 """GPU: the visibility table's records stored as map tiles (csrc/mc_vistab.h
-vis_tiles, mc_env_kernel.hip vis_items_load / vis_items_land): every (agent,
+vis_tiles, mc_env_step.h vis_items_load / vis_items_land): every (agent,
 tile) item of the step kernel loads its own tile of the record of its robot's
 post-move cell, and a reset's initial sense reads the table the same way.
 Every case asserts kernel_variant() first and runs under

@@ -1,6 +1,6 @@
 // VALU issue cost of 64-bit vs 32-bit variable shifts on gfx950 (one wave per
 // SIMD and four, independent chains): for choosing the line-word width of
-// the fan march (csrc/mc_env_kernel.hip fan_pair).
+// the fan march (csrc/mc_env_step.h fan_pair).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
