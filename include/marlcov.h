@@ -337,9 +337,62 @@ int mc_set_minimap_obs(void* env, double* dev_minimap_obs);
  * caller can read at once. */
 int mc_copy_envs(void* dst, void* src, const int32_t* dev_src, void* stream);
 
+/* Global state as dense planes on the device: the tiled bit maps of chosen
+ * envs decoded to uint8, for centralised critics, batch rendering and logging
+ * (the caller would otherwise copy the MC_FIELD_* tiles to the host and unpack
+ * them).  The planes are the reference's state attributes
+ * (dec_grid_rl.py:478-518; its render() draws three of them, :561-580).
+ * `layers` is a mask of MC_MAP_* bits; the planes appear in ascending bit
+ * order, all in padded-grid coordinates, x in [0, width), y in [0, length):
+ *
+ *   bit  name             planes  scale 1 (a cell)              scale 8 (a tile)
+ *   1    MC_MAP_GRID_NEG  1       grid < 0 of the env's pool    such cells of the tile inside
+ *                                 grid (border ring: 1)         the grid (_grid)
+ *   2    MC_MAP_GRID_POS  1       grid > 0                      count
+ *   4    MC_MAP_VISITED   1       _visited                      count
+ *   8    MC_MAP_OBST_ANY  1       OR over agents of _obst_pad   count
+ *                                 (_observed_obstacles)
+ *   16   MC_MAP_ROBOTS    1       i + 1 at robot i's cell, else robots in the tile
+ *                                 0: the true positions of
+ *                                 _robot_pos_map, not the
+ *                                 moved-filtered _robot_pad
+ *   32   MC_MAP_FREE      N       _free_pad[i], agent-major     count
+ *   64   MC_MAP_OBST      N       _obst_pad[i], agent-major     count
+ *
+ * Output: scale 1 uint8 [count][P][width][length]; scale 8 uint8
+ * [count][P][ceil(width/8)][ceil(length/8)] with values 0..64, pooled cell
+ * (i, j) being the 8x8 cells from (8i, 8j) (cells beyond the grid do not
+ * count).  Slot k holds env dev_envs[k] (int32 [count], device; repeated and
+ * unordered indices are fine; NULL: envs 0..num_envs-1 in order, count must be
+ * num_envs).  mc_map_planes returns P for this handle (-1 and the error for a
+ * null env, layers 0 or unknown bits); mc_export_bytes the bytes of the output
+ * (-1 on a bad argument); out_bytes must equal it and dev_out must be 16-byte
+ * aligned.
+ *
+ * Call contract.  Arguments are checked before anything is enqueued (MC_EINVAL,
+ * the message names the argument; MC_ESTATE before the grid pool is set);
+ * count == 0 enqueues nothing.  One kernel launch, stream-ordered and
+ * asynchronous; no allocation, no synchronisation and no host read (capturable
+ * in a graph).  The call reads state only: it never writes the handle, and it
+ * is not an env-kernel launch (mc_env_launches).
+ *
+ * Checked on the device, before any load through the index: dev_envs[k]
+ * outside [0, num_envs) leaves slot k of the output untouched and sets bit 64
+ * of the device error word (mc_check); every valid slot of the same call is
+ * still written.
+ *
+ * Added without raising MARLCOV_ABI_VERSION, like mc_env_launches: the
+ * addition changes no existing symbol or struct. */
+enum { MC_MAP_GRID_NEG = 1, MC_MAP_GRID_POS = 2, MC_MAP_VISITED = 4, MC_MAP_OBST_ANY = 8,
+       MC_MAP_ROBOTS = 16, MC_MAP_FREE = 32, MC_MAP_OBST = 64, MC_MAP_ALL = 127 };
+int32_t mc_map_planes(void* env, uint32_t layers);
+int64_t mc_export_bytes(void* env, uint32_t layers, int32_t scale, int32_t count);
+int mc_export_maps(void* env, uint32_t layers, int32_t scale, const int32_t* dev_envs, int32_t count,
+                   uint8_t* dev_out, int64_t out_bytes, void* stream);
+
 /* Synchronise `stream` and report (then clear) the device error word:
  * 1 = window, 4 = placement failed, 8 = bad injected cell, 32 = mc_copy_envs
- * index. */
+ * index, 64 = mc_export_maps index. */
 int mc_check(void* env, void* stream);
 
 /* ==========================================================================

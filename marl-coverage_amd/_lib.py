@@ -20,6 +20,11 @@ PARAM_DIST_CACHE_CELLS, PARAM_DIST_T, PARAM_DIST_MAX_ROWS = 0, 1, 2  # mc_build_
 ACT_SENTINEL = 255
 ACT_NOOP = 4
 
+# mc_export_maps layer bits, and their names in BatchCoverageEnv.global_state
+(MAP_GRID_NEG, MAP_GRID_POS, MAP_VISITED, MAP_OBST_ANY, MAP_ROBOTS, MAP_FREE, MAP_OBST) = (1 << b for b in range(7))
+MAP_ALL = 127
+MAP_NAMES = ("grid_neg", "grid_pos", "visited", "obst_any", "robots", "free", "obst")  # name k: bit 1 << k
+
 (FIELD_POS, FIELD_MOVED, FIELD_FREE, FIELD_OBST, FIELD_VISITED, FIELD_FREE_COUNT,
  FIELD_VISITED_COUNT, FIELD_CURRSTEP, FIELD_DONE_THRESH, FIELD_ENV_GRID, FIELD_EPISODE,
  FIELD_NUMFREE, FIELD_GRID_NEG, FIELD_GRID_POS, FIELD_DIST_MW, FIELD_DIST_LISTED, FIELD_EP_PC,
@@ -145,6 +150,9 @@ SIGNATURES = [
     ("mc_get_state", ctypes.c_int, [_VP, _I32, _VP, _I64, _VP]),
     ("mc_set_state", ctypes.c_int, [_VP, _I32, _VP, _I64, _VP]),
     ("mc_copy_envs", ctypes.c_int, [_VP, _VP, _VP, _VP]),
+    ("mc_map_planes", _I32, [_VP, ctypes.c_uint32]),
+    ("mc_export_bytes", _I64, [_VP, ctypes.c_uint32, _I32, _I32]),
+    ("mc_export_maps", ctypes.c_int, [_VP, ctypes.c_uint32, _I32, _VP, _I32, _VP, _I64, _VP]),
     ("mc_check", ctypes.c_int, [_VP, _VP]),
     ("mc_debug_stamps", ctypes.c_int, [_VP, _VP]),
     ("mc_set_dist_obs", ctypes.c_int, [_VP, _VP]),
@@ -201,6 +209,7 @@ def load(path: str | None = None):
 
 
 ERR_FORK = 1 << 5  # device error bit of mc_copy_envs / mc_sg_copy_envs (a bad or chained index)
+ERR_EXPORT = 1 << 6  # device error bit of mc_export_maps (an env index outside [0, num_envs))
 
 
 def check(rc: int, what: str = ""):
@@ -209,5 +218,7 @@ def check(rc: int, what: str = ""):
         word = re.search(r"error word 0x([0-9a-fA-F]+)", msg)
         if rc == MC_EDEVICE and word and int(word.group(1), 16) & ERR_FORK:
             msg += ": a fork index was outside [-1, source num_envs) or named an env the same call overwrites"
+        if rc == MC_EDEVICE and word and int(word.group(1), 16) & ERR_EXPORT:
+            msg += ": bit 64, a global_state env index was outside [0, num_envs); its output slot was not written"
         raise MarlcovError(f"{what} failed ({rc}): {msg}")
     return rc

@@ -386,6 +386,81 @@ class BatchCoverageEnv:
                    "mc_set_state")
 
     # ------------------------------------------------------------------
+    def _map_mask(self, layers) -> int:
+        """global_state's ``layers``: an int mask of ``_lib.MAP_*`` bits, a
+        layer name or a sequence of names (``_lib.MAP_NAMES``)."""
+        if isinstance(layers, (int, np.integer)) and not isinstance(layers, bool):
+            if not 0 <= int(layers) < 2 ** 32:
+                raise ValueError(f"layers: mask {layers} is not a uint32")
+            return int(layers)
+        names = (layers,) if isinstance(layers, str) else tuple(layers)
+        mask = 0
+        for n in names:
+            if n not in _lib.MAP_NAMES:
+                raise ValueError(f"layers: unknown layer {n!r} (one of {', '.join(_lib.MAP_NAMES)})")
+            mask |= 1 << _lib.MAP_NAMES.index(n)
+        return mask
+
+    def global_state_planes(self, layers=("visited", "obst_any", "robots")):
+        """The labels of ``global_state``'s planes in output order: the
+        single-plane layers by ascending bit, then ``free0..`` and ``obst0..``
+        (one plane per agent)."""
+        mask = self._map_mask(layers)
+        planes = self.lib.mc_map_planes(self._h, mask)
+        if planes < 0:
+            _lib.check(int(planes), "mc_map_planes")
+        out = [n for k, n in enumerate(_lib.MAP_NAMES[:5]) if mask >> k & 1]
+        for k in (5, 6):
+            if mask >> k & 1:
+                out += [f"{_lib.MAP_NAMES[k]}{i}" for i in range(self.num_agents)]
+        assert len(out) == planes
+        return out
+
+    def global_state(self, layers=("visited", "obst_any", "robots"), envs=None, scale=1, out=None):
+        """The global state of ``envs`` (None: all, else an integer sequence or
+        tensor; slot k of the result is env ``envs[k]``) as a uint8 device
+        tensor [count, P, H, W] in padded-grid coordinates, decoded on the
+        device in one launch (mc_export_maps): the input of a centralised
+        critic, ``critic(env.global_state().float())``.  ``layers``: names out
+        of grid_neg, grid_pos, visited, obst_any, robots (i + 1 at robot i's
+        cell), free, obst (one plane per agent each), or an int mask of
+        ``MAP_*`` bits; ``global_state_planes`` labels the P planes.
+        ``scale=1``: one byte per cell, H x W = width x length.  ``scale=8``:
+        one count (0..64) per 8x8 tile, ceil(width / 8) x ceil(length / 8).
+        ``out``: a contiguous uint8 device tensor of the result's shape to fill
+        instead of a new one.  An index outside [0, num_envs) leaves its slot
+        untouched and makes ``check()`` raise."""
+        torch = self._torch
+        mask = self._map_mask(layers)
+        idx, count = None, self.num_envs
+        if envs is not None:
+            idx = envs if isinstance(envs, torch.Tensor) else torch.as_tensor(np.asarray(envs))
+            if idx.numel() == 0:  # (an empty list has no integer dtype of its own)
+                idx = idx.to(torch.int32)
+            if idx.dim() != 1 or idx.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+                raise ValueError(f"envs must be a 1-D sequence of integers, got {idx.dtype} {list(idx.shape)}")
+            idx = idx.to(device=self.device, dtype=torch.int32).contiguous()
+            count = idx.numel()
+        planes = self.lib.mc_map_planes(self._h, mask)
+        if planes < 0:
+            _lib.check(int(planes), "mc_map_planes")
+        nbytes = self.lib.mc_export_bytes(self._h, mask, int(scale), count)
+        if nbytes < 0:
+            _lib.check(int(nbytes), "mc_export_bytes")
+        H, W = (self.width, self.length) if int(scale) == 1 else (-(-self.width // 8), -(-self.length // 8))
+        shape = (count, planes, H, W)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        elif (tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != torch.device(self.device)
+                or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous uint8 tensor of shape {shape} on {self.device}")
+        if count == 0:
+            return out
+        _lib.check(self.lib.mc_export_maps(self._h, mask, int(scale), None if idx is None else idx.data_ptr(),
+                                           count, out.data_ptr(), nbytes, self._stream()), "mc_export_maps")
+        return out
+
+    # ------------------------------------------------------------------
     def _fork_index(self, src_index, source):
         """fork()'s arguments, checked: the int32 [B] device index tensor."""
         torch = self._torch

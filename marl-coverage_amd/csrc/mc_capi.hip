@@ -16,6 +16,7 @@
 #include "marlcov.h"
 #include "mc_internal.h"
 #include "mc_env_select.h"
+#include "mc_export.h"
 #include "mc_fork.h"
 #include "mc_fuse.h"
 #include "mc_vistab.h"
@@ -47,6 +48,8 @@ size_t dijkstra_lds_bytes(const State& s, int pad);
 size_t dijkstra_big_slot_bytes(const State& s, int pad);
 unsigned dijkstra_big_slots(const State& s, int pad);
 hipError_t launch_minimap(const State& s, int mini, double* out, hipStream_t stream);
+hipError_t launch_export(const State& s, uint32_t layers, int scale, const int32_t* dev_envs, int count,
+                         uint8_t* dev_out, hipStream_t stream);
 __global__ void dijkstra_kernel(State s, int pad, int layer, int Lc, uint8_t* obs_out,
                                 const uint32_t* list, uint32_t* count);
 }  // namespace mc
@@ -1235,6 +1238,58 @@ int mc_copy_envs(void* dst, void* src, const int32_t* dev_src, void* stream) {
   return MC_OK;
 }
 
+// planes / output bytes of an export, -1 (with the message) on a bad argument
+static int64_t export_shape(Env* E, const char* who, uint32_t layers, int32_t scale, int32_t count, int* planes) {
+  if (layers == 0 || (layers & ~mc::kMapAll))
+    return fail(MC_EINVAL, "%s: layers 0x%x selects no plane or has unknown bits (MC_MAP_ALL = 0x%x)", who, layers,
+                mc::kMapAll);
+  if (scale != 1 && scale != 8) return fail(MC_EINVAL, "%s: scale %d is not 1 or 8", who, (int)scale);
+  if (count < 0) return fail(MC_EINVAL, "%s: count %d is negative", who, (int)count);
+  const mc::State& s = E->s;
+  const int P = mc::export_planes(layers, s.N);
+  const int64_t plane = scale == 8 ? (int64_t)s.TR * s.TC : (int64_t)s.Wp * s.Lp;
+  if (plane * P >= 0x7FFFFFFFll)
+    return fail(MC_EINVAL, "%s: layers 0x%x at scale %d are %lld bytes per env (limit 2 GiB)", who, layers,
+                (int)scale, (long long)(plane * P));
+  if (planes) *planes = P;
+  return plane * P * (int64_t)count;
+}
+
+int32_t mc_map_planes(void* env, uint32_t layers) {
+  Env* E = as_env(env);
+  if (!E) return fail(MC_EINVAL, "mc_map_planes: null env");
+  int P = 0;
+  if (export_shape(E, "mc_map_planes", layers, 1, 0, &P) < 0) return MC_EINVAL;
+  return P;
+}
+
+int64_t mc_export_bytes(void* env, uint32_t layers, int32_t scale, int32_t count) {
+  Env* E = as_env(env);
+  if (!E) return fail(MC_EINVAL, "mc_export_bytes: null env");
+  return export_shape(E, "mc_export_bytes", layers, scale, count, nullptr);
+}
+
+int mc_export_maps(void* env, uint32_t layers, int32_t scale, const int32_t* dev_envs, int32_t count,
+                   uint8_t* dev_out, int64_t out_bytes, void* stream) {
+  Env* E = as_env(env);
+  if (!E) return fail(MC_EINVAL, "mc_export_maps: null env");
+  if (!dev_out) return fail(MC_EINVAL, "mc_export_maps: null dev_out");
+  const int64_t bytes = export_shape(E, "mc_export_maps", layers, scale, count, nullptr);
+  if (bytes < 0) return MC_EINVAL;
+  if (!dev_envs && count != E->s.B)
+    return fail(MC_EINVAL, "mc_export_maps: count %d with dev_envs NULL (NULL means all %d envs in order)",
+                (int)count, E->s.B);
+  if (out_bytes != bytes)
+    return fail(MC_EINVAL, "mc_export_maps: out_bytes %lld, the output is %lld bytes (mc_export_bytes)",
+                (long long)out_bytes, (long long)bytes);
+  if ((uintptr_t)dev_out & 15u) return fail(MC_EINVAL, "mc_export_maps: dev_out %p is not 16-byte aligned", (void*)dev_out);
+  if (!E->grids_set) return fail(MC_ESTATE, "mc_export_maps: grids not set (mc_set_grids / mc_generate_grids)");
+  if (count == 0) return MC_OK;
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(mc::launch_export(E->s, layers, scale, dev_envs, count, dev_out, (hipStream_t)stream));
+  return MC_OK;
+}
+
 int mc_set_dist_obs(void* env, float* dev_dist_obs) {
   Env* E = as_env(env);
   if (!E || !dev_dist_obs) return fail(MC_EINVAL, "mc_set_dist_obs: null argument");
@@ -1276,7 +1331,8 @@ int mc_check(void* env, void* stream) {
   if (err) {
     HIP_TRY(hipMemsetAsync(E->s.err, 0, 4, st));
     HIP_TRY(hipStreamSynchronize(st));
-    return fail(MC_EDEVICE, "device error word 0x%x (1=window 4=placement 8=inject 32=copy_envs index)", err);
+    return fail(MC_EDEVICE,
+                "device error word 0x%x (1=window 4=placement 8=inject 32=copy_envs index 64=export_maps index)", err);
   }
   return MC_OK;
 }

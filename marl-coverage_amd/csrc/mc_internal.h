@@ -25,6 +25,7 @@ enum : uint32_t {
   ERR_INJECT = 1u << 3,     // injected start cell invalid (obstacle / clash)
   ERR_FORK = 1u << 5,       // mc_copy_envs: index out of range, or a source env
                             // that the same call overwrites (mc_fork.hip)
+  ERR_EXPORT = 1u << 6,     // mc_export_maps: env index out of range (mc_export.hip)
 };
 
 // One lidar beam, derived on the host from the reference's (xinc, yinc,
