@@ -208,6 +208,12 @@ int mc_random_actions(void* env, uint64_t seed, int32_t step, uint8_t* dev_actio
  * The string stays valid until the calling thread's next call. */
 const char* mc_kernel_variant(void* env);
 
+/* The same instantiation by its row label "lanes,envs per workgroup,word,shape",
+ * e.g. "64,2,uint32_t,ShapeC2BV": unlike the name it tells a bench shape or a
+ * visibility-table shape from its general one.  Diagnostic, for tests that
+ * must run one particular row.  A static string. */
+const char* mc_kernel_label(void* env);
+
 /* Which kernels build the dijkstra_input layer: "window+lds" (the window
  * kernel, then the full-map BFS with its bitboards in LDS for the paths
  * longer than 24 steps), "window+hbm" (the same with the bitboards in a

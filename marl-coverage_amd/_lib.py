@@ -141,6 +141,7 @@ SIGNATURES = [
     ("mc_set_env_grids", ctypes.c_int, [_VP, _VP, _VP]),
     ("mc_random_actions", ctypes.c_int, [_VP, _U64, _I32, _VP, _VP]),
     ("mc_kernel_variant", ctypes.c_char_p, [_VP]),
+    ("mc_kernel_label", ctypes.c_char_p, [_VP]),
     ("mc_dijkstra_variant", ctypes.c_char_p, [_VP]),
     ("mc_reset", ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
     ("mc_step", ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP]),

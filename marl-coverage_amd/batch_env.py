@@ -326,6 +326,11 @@ class BatchCoverageEnv:
         """The env-kernel instantiation mc_step launches (mc_kernel_variant)."""
         return self.lib.mc_kernel_variant(self._h).decode()
 
+    def kernel_label(self) -> str:
+        """The same instantiation by its row label (mc_kernel_label), which
+        tells a bench or table shape from its general one."""
+        return self.lib.mc_kernel_label(self._h).decode()
+
     def env_launches(self) -> int:
         """Env-kernel launches this handle has issued (mc_env_launches): a
         fused ``rollout`` launch of several steps counts once."""

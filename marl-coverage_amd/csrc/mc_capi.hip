@@ -32,6 +32,7 @@ hipError_t launch_pack(const State& s, const int8_t* grids, hipStream_t stream);
 hipError_t launch_gen(const State& s, uint64_t seed, double p, hipStream_t stream);
 hipError_t launch_random_actions(const State& s, uint64_t seed, int step, uint8_t* out, hipStream_t stream);
 const char* env_variant(const State& s, int nt, int epw);
+const char* env_label(const State& s, int nt, int epw);
 bool env_takes_vis_table(const State& s, int nt, int epw);
 hipError_t launch_dijkstra(const State& s, int pad, int layer, int Lc, uint8_t* obs,
                            uint32_t* list, bool window, uint64_t* big, unsigned big_slots,
@@ -979,6 +980,15 @@ const char* mc_kernel_variant(void* env) {
   if (E->s.sensor == MC_SENSOR_LIDAR && E->s.fan_nsec + E->s.fan_nspec > 0)
     name += " +fan(" + std::to_string(E->s.fan_nsec) + "/" + std::to_string(E->s.fan_nspec) + ")";
   return name.c_str();
+}
+
+const char* mc_kernel_label(void* env) {
+  Env* E = as_env(env);
+  if (!E) {
+    fail(MC_EINVAL, "mc_kernel_label: null env");
+    return "";
+  }
+  return mc::env_label(E->s, E->nt, launch_epw(E));
 }
 
 const char* mc_dijkstra_variant(void* env) {

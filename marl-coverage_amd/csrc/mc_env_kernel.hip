@@ -35,6 +35,11 @@ const char* env_variant(const State& s, int nt, int epw) {
   return i < 0 ? "none" : kEnvRows[i].name;
 }
 
+const char* env_label(const State& s, int nt, int epw) {
+  const int i = select_env(s, nt, epw);
+  return i < 0 ? "none" : kEnvRows[i].label;
+}
+
 bool env_takes_vis_table(const State& s, int nt, int epw) { return env_takes_vis_table(s, nt, epw, getenv_spec()); }
 
 hipError_t launch_env(const State& s, int mode, const uint8_t* actions, const uint8_t* env_mask,

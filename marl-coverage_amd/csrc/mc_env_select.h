@@ -106,6 +106,14 @@ struct EnvCfg {
   // record (vis_items), in a step and in a reset's initial sense alike -- such
   // a kernel holds no march at all
   static constexpr bool VISTAB = RAYPROG && SH::VT != 0 && vis_fits(SH::H);
+  // the fused loop carries the lane's constants in registers (LaneK,
+  // mc_env_step.h) instead of deriving them from the lane id in every step:
+  // the one-wave kernels of the compiled shapes
+  static constexpr bool LANEK = NT == 64 && NSM > 0;
+  // the same kernels keep a staged tile's index in a register from stage_load
+  // to store_tiles instead of computing it twice (two VGPRs per lane: the
+  // C4 bench kernel, at 128, has none to give)
+  static constexpr bool KEEP_GT = LANEK;
 };
 
 // ---- the instantiations: X(NT, EPW, word, shape, public name), one row per

@@ -176,6 +176,22 @@ __device__ __forceinline__ int row_word(const State& s, int a, int lx) {
   return sizeof(WT) == 4 ? lx * (s.N | 1) + a : a * (8 * s.TW + 1) + lx;
 }
 
+// What write_obs_fast's lane does, from the lane id and the launch's shape
+// alone (obs_roles): the crop it builds, and (X3 layout) where the three
+// dwords it stores come from.
+struct ObsRoles {
+  int a, layer;  // crop lane: the crop's agent and layer
+  int src, o;    // triple lane: the lane holding its first crop, its first bit in that crop
+  int store;     // triple lane: it has a triple of an env of the batch
+  // one word of bit fields (a < 8: LANEK kernels have at most 8 agents)
+  __device__ __forceinline__ uint32_t pack() const {
+    return (uint32_t)a | (uint32_t)layer << 3 | (uint32_t)src << 5 | (uint32_t)o << 11 | (uint32_t)store << 16;
+  }
+  __device__ static __forceinline__ ObsRoles unpack(uint32_t w) {
+    return {(int)(w & 7u), (int)(w >> 3 & 3u), (int)(w >> 5 & 63u), (int)(w >> 11 & 31u), (int)(w >> 16)};
+  }
+};
+
 // One env slot of the workgroup, on top of everything fixed at compile time for
 // its env_kernel<NT, EPW, WT, SH> instantiation (EnvCfg, mc_env_select.h): the
 // device functions take a `const CT& C` and read their constants from CT, not
@@ -187,7 +203,17 @@ struct Ctx : EnvCfg<NT_, EPW_, WT_, SH_> {
   int lane;   // lane within the wave
   int lane0;  // first lane of this env's slot within the wave
   int e;      // env index
+  ObsRoles ob;  // OBS_FAST
   Lds<WT_> L;
+};
+
+// The lane constants the fused loop carries from step to step (EnvCfg::LANEK):
+// functions of threadIdx, blockIdx and the launch's shape alone, so a reset, a
+// sentinel or a chunk boundary cannot make them stale.  env_kernel passes each
+// member through an empty asm at the top of every iteration: the value stays
+// in its VGPR, and nothing derived from it is loop-invariant to the compiler.
+struct LaneK {
+  uint32_t ob;  // the lane's ObsRoles, packed
 };
 
 // broadcast lane (lane0 + i)'s value of v to the slot
@@ -218,6 +244,7 @@ struct Items {
   uint64_t n[KI];                   // grid < 0 tiles (raw load; outside the map: all ones after stage_scatter)
   uint64_t p[KI];                   // grid > 0 tiles (square sensor)
   int ti[KI], tj[KI];               // tile within the agent's block
+  uint32_t gt[KI];                  // KEEP_GT: tile_index24 of (gi, gj) where `in`, from stage_load to store_tiles
   bool masks;                       // f / o / u were loaded (else known zero)
 };
 
@@ -394,6 +421,7 @@ __device__ __forceinline__ void stage_load(const State& s, const CT& C, int g, b
     I.in[k] = (idx < items) & ((unsigned)gi < (unsigned)s.TR) & ((unsigned)gj < (unsigned)s.TC);
     gt[k] = tile_index24(s.TCS, I.in[k] ? gi : 0, I.in[k] ? gj : 0);
     // tiles outside the map read the mask arrays' zero tile (mc_create)
+    if constexpr (CT::KEEP_GT) I.gt[k] = gt[k];
     fw[k] = I.in[k] ? __umul24(eN + (uint32_t)I.a[k], mt) + gt[k] : zf;
     vk[k] = I.in[k] ? vw + gt[k] : zv;
   }
@@ -1680,10 +1708,12 @@ __device__ __forceinline__ void store_tiles(const State& s, const CT& C, const I
 #pragma unroll
   for (int k = 0; k < KI; ++k) {
     if (!I.in[k]) continue;
-    const uint32_t gt = tile_index24(s.TCS, I.gi[k], I.gj[k]);
-    const uint32_t fb = __umul24((uint32_t)C.e * (uint32_t)s.N + (uint32_t)I.a[k], mt) + gt;
     // only obstacle marks can fall on an edge tile's cells beyond the map
     const uint64_t no = I.no[k] & tile_in_grid(s, I.gi[k], I.gj[k]);
+    uint32_t gt;  // (in: the tile's own index)
+    if constexpr (CT::KEEP_GT) gt = I.gt[k];
+    else gt = tile_index24(s.TCS, I.gi[k], I.gj[k]);
+    const uint32_t fb = __umul24((uint32_t)C.e * (uint32_t)s.N + (uint32_t)I.a[k], mt) + gt;
     if (I.nf[k]) st_tile<O32>(s.freem, fb, I.f[k] | I.nf[k]);  // one writer per agent tile
     if (no) st_tile<O32>(s.obstm, fb, I.o[k] | no);
     if (I.nu[k]) {  // agents' blocks overlap: several lanes may add bits to one tile
@@ -1703,6 +1733,11 @@ __device__ __forceinline__ void store_tiles(const State& s, const CT& C, const I
 // workgroup only: the two-env C2 wave spilled more with it and ran slower
 // (8.38 vs 8.22 us; C4 126.6 -> 123.3 us, C5 steady 140.7 -> 136.4 us per
 // step, profiles/r6/rlab/)
+// ... and, LOOP, the loop copy of the one-wave compiled kernels (steps 1.. of
+// a fused launch), whose argument lines are warm in the scalar cache: kept
+// live across a step, the State's pointers and the buffers cost the C2 bench
+// kernel 41 spilled SGPRs, ~10 v_writelane and ~40 v_readlane per step; re-read
+// at the phase boundaries, 2 (profiles/r16/step_diet/)
 // The env kernel's one argument: the State and the step's buffers
 struct EnvIO {
   const uint8_t* actions;   // [B][N] (MODE_STEP)
@@ -1740,9 +1775,9 @@ __device__ __forceinline__ const EnvArgs& kernarg_env_args() {
   return *(const EnvArgs*)kp;
 }
 // k: the step of the launch (the buffers' offsets are applied again)
-template <class SH, int EPW>
+template <class SH, int EPW, bool LOOP = false>
 __device__ __forceinline__ void reload_state(State& s, EnvIO& io, int k) {
-  if constexpr (EPW == 1) {
+  if constexpr (EPW == 1 || LOOP) {
     const EnvArgs& A = kernarg_env_args();
     s = A.s;
     io = io_at_step(A.io, k);
@@ -2016,7 +2051,43 @@ __device__ __forceinline__ void write_obs(const State& s, const CT& C, uint8_t* 
 // wave's envs are consecutive, so their obs are one run of dwords: lane l
 // writes dwords l, l + 64, ...; dword d is the nibble at bit 4d of the
 // slot's crop stream (fetched from the crop lanes by ds_bpermute), spread to
-// bytes by one multiply.  No per-row or per-layer branches.
+// bytes by one multiply.  No per-row or per-layer branches.  What a lane does
+// in all this follows from its place alone (obs_roles): the fused loop
+// computes it once per launch (LaneK).
+// the layout of the stores
+template <class CT>
+struct ObsLay {
+  using OF = ObsFast<CT::SH::EGO, CT::SH::N, CT::SH::LC>;
+  static constexpr int DPE = OF::NB * OF::EE / 4;  // dwords per env (a cell is one byte)
+  // three dwords per lane when an env's run is whole triples and the wave's
+  // triples fit 64 lanes (C2: 25 per env): one pair of ds_bpermutes and one
+  // global_store_dwordx3 per lane; a triple's 12 bits span at most two crops
+  static constexpr int TPE = DPE / 3;  // dword triples per env
+  static constexpr bool X3 = CT::NT == 64 && DPE % 3 == 0 && CT::EPW * TPE <= 64 && OF::EE >= 12;
+};
+
+template <class CT>
+__device__ __forceinline__ ObsRoles obs_roles(const State& s, int sub, int lane) {
+  ObsRoles R = {0, 0, 0, 0, 0};
+  if constexpr (CT::OBS_FAST) {
+    constexpr int EPW = CT::EPW, LPE = CT::LPE, LC = CT::SH::LC;
+    using OL = ObsLay<CT>;
+    constexpr int EE = OL::OF::EE, NB = OL::OF::NB, TPE = OL::TPE;
+    const int j = sub < NB ? sub : 0;
+    R.a = LC == 3 ? (j * 86) >> 8 : j >> 2;  // j / LC for j < 128
+    R.layer = j - LC * R.a;
+    if constexpr (OL::X3) {
+      const int es = EPW == 1 ? 0 : lane / TPE;  // env slot of the lane's triple
+      const int b0 = 12 * (lane - es * TPE);     // its first bit within that env's stream
+      const int jb = b0 / EE;
+      R.o = b0 - jb * EE;
+      R.src = es * LPE + jb;
+      R.store = lane < EPW * TPE && (int)blockIdx.x * EPW + es < s.B;
+    }
+  }
+  return R;
+}
+
 template <class CT, typename WT = typename CT::WT>
 __device__ __forceinline__ void write_obs_fast(const State& s, const CT& C, uint8_t* obs_out) {
   constexpr int NT = CT::NT, EPW = CT::EPW, LPE = CT::LPE;
@@ -2028,9 +2099,7 @@ __device__ __forceinline__ void write_obs_fast(const State& s, const CT& C, uint
   const Lds<WT>& L = C.L;
   const int TW = s.TW;
   // ---- crops
-  const int j = C.sub < NB ? C.sub : 0;
-  const int a = LC == 3 ? (j * 86) >> 8 : j >> 2;  // j / LC for j < 128
-  const int layer = j - LC * a;
+  const int a = C.ob.a, layer = C.ob.layer;
   const int xa = L.x[a], ya = L.y[a];
   const uint64_t moved = L.sc->moved;
   uint32_t rp = 0;  // layer 0: robot_pad crop (robots that moved since the reset)
@@ -2086,25 +2155,17 @@ __device__ __forceinline__ void write_obs_fast(const State& s, const CT& C, uint
     return;
   }
   // ---- dwords of the wave's obs run
-  constexpr int DPE = NB * EE / 4;       // dwords per env (a cell is one byte)
+  constexpr int DPE = ObsLay<CT>::DPE;   // dwords per env (a cell is one byte)
   constexpr int D = EPW * DPE;           // dwords per wave
   const int e_first = blockIdx.x * EPW;  // the wave's first env
   uint32_t* out = reinterpret_cast<uint32_t*>(obs_out + (size_t)e_first * (NB * EE));
   const int lane = C.lane;
-  // three dwords per lane when an env's run is whole triples and the wave's
-  // triples fit 64 lanes (C2: 25 per env): one pair of ds_bpermutes and one
-  // global_store_dwordx3 per lane; a triple's 12 bits span at most two crops
-  constexpr int TPE = DPE / 3;  // dword triples per env
-  constexpr bool X3 = DPE % 3 == 0 && EPW * TPE <= 64 && EE >= 12;
-  if constexpr (X3) {
-    const int es = EPW == 1 ? 0 : lane / TPE;  // env slot of the lane's triple
-    const int b0 = 12 * (lane - es * TPE);     // its first bit within that env's stream
-    const int jb = b0 / EE, o = b0 - jb * EE;
-    const int src = es * LPE + jb;
+  if constexpr (ObsLay<CT>::X3) {  // a dword triple per lane, its place from obs_roles
+    const int src = C.ob.src, o = C.ob.o;
     const uint32_t w0 = (uint32_t)__shfl((int)crop, src);
     const uint32_t w1 = (uint32_t)__shfl((int)crop, src + 1 < 64 ? src + 1 : src);
     const uint32_t bits = (uint32_t)((((uint64_t)w1 << EE) | w0) >> o);
-    if (lane < EPW * TPE && e_first + es < s.B) {
+    if (C.ob.store) {
       typedef uint32_t u32x3 __attribute__((ext_vector_type(3), aligned(4)));
       u32x3 v;
       v.x = ((bits & 0xFu) * 0x00204081u) & 0x01010101u;
@@ -2151,7 +2212,7 @@ constexpr int env_min_waves() {
 // One step (or the reset) of the slot's env: step k of the launch, with io the
 // launch's buffers as step k sees them (io_at_step).  `valid`: the slot has an
 // env (a short last workgroup's idle slot writes nothing, in any step).
-template <class CT>
+template <class CT, bool LOOP = false>
 __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool valid, const int k) {
   using WT = typename CT::WT;
   using SH = typename CT::SH;
@@ -2272,7 +2333,7 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
     for (int b = C.sub + LPE; b < s.nbeams; b += LPE) L.beams[b] = s.beams[b];
   }
   __syncthreads();
-  reload_state<SH, EPW>(s, io, k);
+  reload_state<SH, EPW, LOOP>(s, io, k);
 
   if (active) {
     STAMP(1);
@@ -2338,7 +2399,7 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
     const int numfree = el<O32>(s.numfree, g0);
     __syncthreads();
     STAMP(2);
-    reload_state<SH, EPW>(s, io, k);
+    reload_state<SH, EPW, LOOP>(s, io, k);
     // (the same loop on the scalar unit, robots read by v_readlane, was
     // slower: 10.17 vs 9.83 us at C2 -- +178 SALU for -17 VALU per wave)
     if constexpr (!FRONT && !EARLY) {  // (FRONT, EARLY: moved during round trip 2)
@@ -2358,7 +2419,7 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
       __syncthreads();
     }
     STAMP(3);
-    reload_state<SH, EPW>(s, io, k);
+    reload_state<SH, EPW, LOOP>(s, io, k);
     // dist_reward: lane i < N loads its agent's PRE terms (the last step's
     // dist kernels wrote them) now that its move is known; they land during
     // the sensing (kPrePrefetch: compiled shapes)
@@ -2387,7 +2448,7 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
     sense_and_merge<CT, CT::VISTAB>(s, C, I);
     __syncthreads();
     STAMP(5);
-    reload_state<SH, EPW>(s, io, k);
+    reload_state<SH, EPW, LOOP>(s, io, k);
     // every lane of the slot computes the reward and done (the same values:
     // no broadcast round trip or barrier before the stores); lane 0 stores
     bool do_reset;
@@ -2477,7 +2538,7 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
     // writes (one wave: its LDS operations complete in order)
     if constexpr (NT > 64) __syncthreads();
     STAMP(6);
-    reload_state<SH, EPW>(s, io, k);
+    reload_state<SH, EPW, LOOP>(s, io, k);
     if (!do_reset) {
       store_tiles(s, C, I);
       STAMP(7);
@@ -2485,7 +2546,7 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
       reset_env(s, C, nullptr);  // the finished episode's tiles are not stored
     }
   } else if (reset_req || sent_reset) {
-    reload_state<SH, EPW>(s, io, k);
+    reload_state<SH, EPW, LOOP>(s, io, k);
     if (C.sub == 0 && sentinel) sentinel_done(s, io, e, g0, free_old, currstep0);
     reset_env(s, C, reset_req ? io.inj_pos : nullptr);
     dlist = s.dist && C.sub < N;  // fresh maps: M unknown
@@ -2496,7 +2557,7 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
     // plane is scattered.  With the fan march the column planes overlay
     // fold / oold (carve), and a multi-wave slot's column-byte stores would
     // race with another wave's stage_fold stores.
-    reload_state<SH, EPW>(s, io, k);
+    reload_state<SH, EPW, LOOP>(s, io, k);
     Items<KI> I;
     stage_load(s, C, g0, true, I);
     stage_fold(s, C, I);
@@ -2563,19 +2624,21 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
     }
   }
   STAMP(8);
-  reload_state<SH, EPW>(s, io, k);
+  reload_state<SH, EPW, LOOP>(s, io, k);
   if constexpr (CT::OBS_FAST) {
     if (MC_ABL != 4) write_obs_fast(s, C, io.obs_out);  // every lane of the workgroup
   } else {
     if (valid) write_obs(s, C, io.obs_out);
   }
   STAMP(9);
-  if (valid && io.adj_out != nullptr) {  // updateCommmunicationGraph (:374-391)
-    uint8_t* ad = io.adj_out + (size_t)e * N * N;
-    for (int idx = C.sub; idx < N * N; idx += LPE) {
-      const int i = idx / N, j = idx - i * N;
-      const int dx = abs(L.x[i] - L.x[j]), dy = abs(L.y[i] - L.y[j]);
-      ad[idx] = (max(dx, dy) <= s.comm_r) ? 1 : 0;
+  if (io.adj_out != nullptr) {  // updateCommmunicationGraph (:374-391); the uniform test first
+    if (valid) {
+      uint8_t* ad = io.adj_out + (size_t)e * N * N;
+      for (int idx = C.sub; idx < N * N; idx += LPE) {
+        const int i = idx / N, j = idx - i * N;
+        const int dx = abs(L.x[i] - L.x[j]), dy = abs(L.y[i] - L.y[j]);
+        ad[idx] = (max(dx, dy) <= s.comm_r) ? 1 : 0;
+      }
     }
   }
 #ifdef MC_STAMPS
@@ -2615,8 +2678,10 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
     const size_t slot_lds =
         state_lds_bytes(s, (int)sizeof(WT));
     C.L = carve<WT>(smem + slot * slot_stride(slot_lds), s);
+    C.ob = obs_roles<CT>(s, C.sub, C.lane);
     return valid;
   };
+  [[maybe_unused]] LaneK K = {};  // LANEK: step 0's lane constants, carried through the loop
   // ---- step 0 (mc_step, mc_reset: the only one), straight-line: the kernel
   // arguments as the compiler likes to load them, all at the entry
   {
@@ -2625,6 +2690,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
     EnvIO io = args.io;
     CT C;
     const bool valid = place(s, threadIdx.x, C);
+    if constexpr (CT::LANEK) K.ob = C.ob.pack();
     env_step(s, io, C, valid, 0);
   }
   // ---- steps 1 .. num_steps - 1 of a fused launch: a second copy of the step
@@ -2651,11 +2717,17 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
     // lane-dependent is loop-invariant to the compiler, which would otherwise
     // hoist a step's addresses and masks out of the loop and keep them in
     // registers across it
+    // (LANEK: but for the constants the loop carries on purpose, each made
+    // opaque the same way)
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));
     CT C;
     const bool valid = place(s, tid, C);
-    env_step(s, io, C, valid, k);
+    if constexpr (CT::LANEK) {
+      asm volatile("" : "+v"(K.ob));
+      C.ob = ObsRoles::unpack(K.ob);
+    }
+    env_step<CT, CT::LANEK>(s, io, C, valid, k);
   }
 }
 
