@@ -396,9 +396,57 @@ int64_t mc_export_bytes(void* env, uint32_t layers, int32_t scale, int32_t count
 int mc_export_maps(void* env, uint32_t layers, int32_t scale, const int32_t* dev_envs, int32_t count,
                    uint8_t* dev_out, int64_t out_bytes, void* stream);
 
+/* The inverse of mc_export_maps at scale 1: dense planes set the maps and the
+ * positions of chosen envs, and the library derives what follows from them.
+ * `layers` is a non-empty subset of MC_MAP_IMPORTABLE (robots, free, obst);
+ * any other bit is MC_EINVAL (VISITED and OBST_ANY are derived from the agents'
+ * maps, GRID_NEG and GRID_POS belong to the pool).
+ *
+ * Input: uint8 [count][P][width][length] in padded-grid coordinates, P =
+ * mc_map_planes(env, layers), the planes in mc_export_maps' order for the same
+ * mask (robots, free0..freeN-1, obst0..obstN-1).  Slot k goes to env
+ * dev_envs[k] (int32 [count], device; NULL: envs 0..num_envs-1 in order, count
+ * must be num_envs).  The entries of dev_envs must be distinct: the state of an
+ * env named twice is unspecified after the call (the device does not check
+ * it).  dev_in needs no alignment.  mc_import_bytes returns the bytes of the
+ * input (-1 on a bad argument); in_bytes must equal it.
+ *
+ * What a slot writes.  FREE / OBST: every tile of every agent's map takes the
+ * plane's cells (a nonzero byte is a set bit: 0/1, 0/255 and bool masks all
+ * work; bits beyond the grid stay clear).  With FREE, VISITED becomes the OR
+ * over agents of the new free maps, VISITED_COUNT its popcount and FREE_COUNT
+ * the sum of the agents' popcounts.  ROBOTS: POS[i] becomes the cell whose byte
+ * is i + 1.  With dist_reward, DIST_MW and the top-cell cache header of the
+ * imported envs become -1 (what mc_set_state does for every env) and the PRE
+ * terms are recomputed at the next step.  Nothing else changes: MOVED,
+ * CURRSTEP, DONE_THRESH, ENV_GRID, EPISODE and the episode record stay
+ * (mc_set_state, or a masked mc_reset before the import: "start an episode
+ * from this map" is mc_reset(env_mask) followed by mc_import_maps).  Free and
+ * obstacle cells are not validated against the grid, as with mc_set_state.
+ *
+ * Call contract: as mc_export_maps (arguments checked before anything is
+ * enqueued, MC_EINVAL naming the argument, MC_ESTATE before the grid pool is
+ * set; count == 0 enqueues nothing; one kernel launch, stream-ordered and
+ * asynchronous; no allocation, synchronisation or host read; not an env-kernel
+ * launch).
+ *
+ * Checked on the device, before any store to the slot's env: dev_envs[k]
+ * outside [0, num_envs); and with ROBOTS a byte above N, a robot number absent
+ * or present twice, a robot on a cell where the env's pool grid is < 0, or an
+ * env whose env_grid is outside the pool.  Such a slot leaves its env entirely
+ * untouched and sets bit 128 of the device error word (mc_check); every valid
+ * slot of the same call is still applied.
+ *
+ * Added without raising MARLCOV_ABI_VERSION, like mc_export_maps. */
+enum { MC_MAP_IMPORTABLE = MC_MAP_ROBOTS | MC_MAP_FREE | MC_MAP_OBST };
+int64_t mc_import_bytes(void* env, uint32_t layers, int32_t count);
+int mc_import_maps(void* env, uint32_t layers, const int32_t* dev_envs, int32_t count,
+                   const uint8_t* dev_in, int64_t in_bytes, void* stream);
+
 /* Synchronise `stream` and report (then clear) the device error word:
  * 1 = window, 4 = placement failed, 8 = bad injected cell, 32 = mc_copy_envs
- * index, 64 = mc_export_maps index. */
+ * index, 64 = mc_export_maps index, 128 = mc_import_maps index or robots
+ * plane. */
 int mc_check(void* env, void* stream);
 
 /* ==========================================================================

@@ -9,7 +9,7 @@ the C ABI of ``include/marlcov.h`` with ctypes.  Import it as ``marlcov``
 from .sensors import LidarSensor, SquareSensor, beam_angles, beam_increments  # noqa: F401
 from .gridmaker import gridgen, gridload  # noqa: F401
 from .action_spaces import Continuous, Discrete  # noqa: F401
-from ._lib import (MAP_ALL, MAP_FREE, MAP_GRID_NEG, MAP_GRID_POS, MAP_NAMES, MAP_OBST,  # noqa: F401
+from ._lib import (MAP_ALL, MAP_FREE, MAP_GRID_NEG, MAP_GRID_POS, MAP_IMPORTABLE, MAP_NAMES, MAP_OBST,  # noqa: F401
                    MAP_OBST_ANY, MAP_ROBOTS, MAP_VISITED)
 
 

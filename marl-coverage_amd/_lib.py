@@ -23,6 +23,7 @@ ACT_NOOP = 4
 # mc_export_maps layer bits, and their names in BatchCoverageEnv.global_state
 (MAP_GRID_NEG, MAP_GRID_POS, MAP_VISITED, MAP_OBST_ANY, MAP_ROBOTS, MAP_FREE, MAP_OBST) = (1 << b for b in range(7))
 MAP_ALL = 127
+MAP_IMPORTABLE = MAP_ROBOTS | MAP_FREE | MAP_OBST  # the layers mc_import_maps takes (112)
 MAP_NAMES = ("grid_neg", "grid_pos", "visited", "obst_any", "robots", "free", "obst")  # name k: bit 1 << k
 
 (FIELD_POS, FIELD_MOVED, FIELD_FREE, FIELD_OBST, FIELD_VISITED, FIELD_FREE_COUNT,
@@ -154,6 +155,8 @@ SIGNATURES = [
     ("mc_map_planes", _I32, [_VP, ctypes.c_uint32]),
     ("mc_export_bytes", _I64, [_VP, ctypes.c_uint32, _I32, _I32]),
     ("mc_export_maps", ctypes.c_int, [_VP, ctypes.c_uint32, _I32, _VP, _I32, _VP, _I64, _VP]),
+    ("mc_import_bytes", _I64, [_VP, ctypes.c_uint32, _I32]),
+    ("mc_import_maps", ctypes.c_int, [_VP, ctypes.c_uint32, _VP, _I32, _VP, _I64, _VP]),
     ("mc_check", ctypes.c_int, [_VP, _VP]),
     ("mc_debug_stamps", ctypes.c_int, [_VP, _VP]),
     ("mc_set_dist_obs", ctypes.c_int, [_VP, _VP]),
@@ -211,6 +214,7 @@ def load(path: str | None = None):
 
 ERR_FORK = 1 << 5  # device error bit of mc_copy_envs / mc_sg_copy_envs (a bad or chained index)
 ERR_EXPORT = 1 << 6  # device error bit of mc_export_maps (an env index outside [0, num_envs))
+ERR_IMPORT = 1 << 7  # device error bit of mc_import_maps (a bad env index or robots plane)
 
 
 def check(rc: int, what: str = ""):
@@ -221,5 +225,8 @@ def check(rc: int, what: str = ""):
             msg += ": a fork index was outside [-1, source num_envs) or named an env the same call overwrites"
         if rc == MC_EDEVICE and word and int(word.group(1), 16) & ERR_EXPORT:
             msg += ": bit 64, a global_state env index was outside [0, num_envs); its output slot was not written"
+        if rc == MC_EDEVICE and word and int(word.group(1), 16) & ERR_IMPORT:
+            msg += (": bit 128, a set_global_state env index was outside [0, num_envs) or its robots plane did not "
+                    "hold every robot number once on a cell with grid >= 0; that env was left untouched")
         raise MarlcovError(f"{what} failed ({rc}): {msg}")
     return rc

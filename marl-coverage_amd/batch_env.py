@@ -465,6 +465,53 @@ class BatchCoverageEnv:
                                            count, out.data_ptr(), nbytes, self._stream()), "mc_export_maps")
         return out
 
+    def set_global_state(self, planes, layers=("robots", "free", "obst"), envs=None):
+        """The inverse of ``global_state`` at scale 1 (mc_import_maps): the
+        maps and positions of ``envs`` (None: all, else an integer sequence or
+        tensor of distinct indices; slot k of ``planes`` goes to env
+        ``envs[k]``) from dense planes, packed on the device in one launch.
+        ``layers``: names out of robots, free, obst, or an int mask of those
+        ``MAP_*`` bits (``MAP_IMPORTABLE``); ``planes``: a device tensor, or
+        anything ``torch.as_tensor`` takes, of shape [count, P, width, length]
+        in ``global_state``'s plane order for the same layers (a nonzero cell
+        is set; the robots plane holds i + 1 at robot i's cell).  The library
+        derives the rest: with free, VISITED and the two counters; with
+        dist_reward the imported envs' distance caches are dropped.  Step
+        counter, threshold, moved mask and episode stay as they are: to start
+        an episode from a map, ``reset(env_mask)`` first.  A bad index or
+        robots plane (a number missing, twice, above num_agents or on an
+        obstacle of the grid) leaves its env untouched and makes ``check()``
+        raise; a host ``envs`` with a repeated index raises ValueError (a
+        device tensor is not inspected: the state of an env named twice is
+        unspecified)."""
+        torch = self._torch
+        mask = self._map_mask(layers)
+        idx, count = None, self.num_envs
+        if envs is not None:
+            if not isinstance(envs, torch.Tensor):
+                host = np.asarray(envs).ravel().tolist()
+                if len(set(host)) != len(host):
+                    raise ValueError(f"envs names an env twice: {sorted(e for e in set(host) if host.count(e) > 1)}")
+            idx = envs if isinstance(envs, torch.Tensor) else torch.as_tensor(np.asarray(envs))
+            if idx.numel() == 0:  # (an empty list has no integer dtype of its own)
+                idx = idx.to(torch.int32)
+            if idx.dim() != 1 or idx.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+                raise ValueError(f"envs must be a 1-D sequence of integers, got {idx.dtype} {list(idx.shape)}")
+            idx = idx.to(device=self.device, dtype=torch.int32).contiguous()
+            count = idx.numel()
+        nbytes = self.lib.mc_import_bytes(self._h, mask, count)
+        if nbytes < 0:
+            _lib.check(int(nbytes), "mc_import_bytes")
+        shape = (count, self.lib.mc_map_planes(self._h, mask), self.width, self.length)
+        t = planes if isinstance(planes, torch.Tensor) else torch.as_tensor(np.asarray(planes))
+        if tuple(t.shape) != shape:
+            raise ValueError(f"planes must have shape {shape}, got {tuple(t.shape)}")
+        t = t.to(self.device).to(torch.uint8).contiguous()
+        if count == 0:
+            return
+        _lib.check(self.lib.mc_import_maps(self._h, mask, None if idx is None else idx.data_ptr(), count,
+                                           t.data_ptr(), nbytes, self._stream()), "mc_import_maps")
+
     # ------------------------------------------------------------------
     def _fork_index(self, src_index, source):
         """fork()'s arguments, checked: the int32 [B] device index tensor."""

@@ -19,6 +19,7 @@
 #include "mc_export.h"
 #include "mc_fork.h"
 #include "mc_fuse.h"
+#include "mc_import.h"
 #include "mc_vistab.h"
 
 namespace mc {
@@ -51,6 +52,8 @@ unsigned dijkstra_big_slots(const State& s, int pad);
 hipError_t launch_minimap(const State& s, int mini, double* out, hipStream_t stream);
 hipError_t launch_export(const State& s, uint32_t layers, int scale, const int32_t* dev_envs, int count,
                          uint8_t* dev_out, hipStream_t stream);
+hipError_t launch_import(const State& s, uint32_t layers, const int32_t* dev_envs, int count, const uint8_t* dev_in,
+                         hipStream_t stream);
 __global__ void dijkstra_kernel(State s, int pad, int layer, int Lc, uint8_t* obs_out,
                                 const uint32_t* list, uint32_t* count);
 }  // namespace mc
@@ -1300,6 +1303,54 @@ int mc_export_maps(void* env, uint32_t layers, int32_t scale, const int32_t* dev
   return MC_OK;
 }
 
+// input bytes of an import, -1 (with the message) on a bad argument
+static int64_t import_shape(Env* E, const char* who, uint32_t layers, int32_t count) {
+  if (layers == 0) return fail(MC_EINVAL, "%s: layers 0x0 selects no plane (MC_MAP_IMPORTABLE = 0x%x)", who, mc::kMapImportable);
+  if (const uint32_t other = layers & ~mc::kMapImportable) {
+    static const char* const names[7] = {"MC_MAP_GRID_NEG", "MC_MAP_GRID_POS", "MC_MAP_VISITED", "MC_MAP_OBST_ANY",
+                                         "MC_MAP_ROBOTS",   "MC_MAP_FREE",     "MC_MAP_OBST"};
+    const uint32_t bit = other & (0u - other);  // the lowest one
+    const int b = __builtin_ctz(bit);
+    if (b >= 7) return fail(MC_EINVAL, "%s: layers 0x%x has the unknown bit %u", who, layers, bit);
+    return fail(MC_EINVAL, "%s: layers 0x%x has bit %u (%s), which %s (MC_MAP_IMPORTABLE = 0x%x)", who, layers, bit,
+                names[b], b < 2 ? "belongs to the grid pool" : "is derived from the agents' maps", mc::kMapImportable);
+  }
+  if (count < 0) return fail(MC_EINVAL, "%s: count %d is negative", who, (int)count);
+  const mc::State& s = E->s;
+  const int P = mc::export_planes(layers, s.N);
+  const int64_t plane = (int64_t)s.Wp * s.Lp;
+  if (plane * P >= 0x7FFFFFFFll)
+    return fail(MC_EINVAL, "%s: layers 0x%x are %lld bytes per env (limit 2 GiB)", who, layers, (long long)(plane * P));
+  return plane * P * (int64_t)count;
+}
+
+int64_t mc_import_bytes(void* env, uint32_t layers, int32_t count) {
+  Env* E = as_env(env);
+  if (!E) return fail(MC_EINVAL, "mc_import_bytes: null env");
+  return import_shape(E, "mc_import_bytes", layers, count);
+}
+
+int mc_import_maps(void* env, uint32_t layers, const int32_t* dev_envs, int32_t count, const uint8_t* dev_in,
+                   int64_t in_bytes, void* stream) {
+  Env* E = as_env(env);
+  if (!E) return fail(MC_EINVAL, "mc_import_maps: null env");
+  if (!dev_in) return fail(MC_EINVAL, "mc_import_maps: null dev_in");
+  const int64_t bytes = import_shape(E, "mc_import_maps", layers, count);
+  if (bytes < 0) return MC_EINVAL;
+  if (!dev_envs && count != E->s.B)
+    return fail(MC_EINVAL, "mc_import_maps: count %d with dev_envs NULL (NULL means all %d envs in order)",
+                (int)count, E->s.B);
+  if (in_bytes != bytes)
+    return fail(MC_EINVAL, "mc_import_maps: in_bytes %lld, the input is %lld bytes (mc_import_bytes)",
+                (long long)in_bytes, (long long)bytes);
+  if (!E->grids_set) return fail(MC_ESTATE, "mc_import_maps: grids not set (mc_set_grids / mc_generate_grids)");
+  if (count == 0) return MC_OK;
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(mc::launch_import(E->s, layers, dev_envs, count, dev_in, (hipStream_t)stream));
+  E->dist_pre_stale = true;  // imported maps / positions: recompute the PRE terms
+  return MC_OK;
+}
+
 int mc_set_dist_obs(void* env, float* dev_dist_obs) {
   Env* E = as_env(env);
   if (!E || !dev_dist_obs) return fail(MC_EINVAL, "mc_set_dist_obs: null argument");
@@ -1342,7 +1393,9 @@ int mc_check(void* env, void* stream) {
     HIP_TRY(hipMemsetAsync(E->s.err, 0, 4, st));
     HIP_TRY(hipStreamSynchronize(st));
     return fail(MC_EDEVICE,
-                "device error word 0x%x (1=window 4=placement 8=inject 32=copy_envs index 64=export_maps index)", err);
+                "device error word 0x%x (1=window 4=placement 8=inject 32=copy_envs index 64=export_maps index "
+                "128=import_maps index or robots plane)",
+                err);
   }
   return MC_OK;
 }

@@ -26,6 +26,8 @@ enum : uint32_t {
   ERR_FORK = 1u << 5,       // mc_copy_envs: index out of range, or a source env
                             // that the same call overwrites (mc_fork.hip)
   ERR_EXPORT = 1u << 6,     // mc_export_maps: env index out of range (mc_export.hip)
+  ERR_IMPORT = 1u << 7,     // mc_import_maps: env index out of range, or a robots
+                            // plane that names no valid start cells (mc_import.hip)
 };
 
 // One lidar beam, derived on the host from the reference's (xinc, yinc,
