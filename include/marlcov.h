@@ -443,6 +443,50 @@ int64_t mc_import_bytes(void* env, uint32_t layers, int32_t count);
 int mc_import_maps(void* env, uint32_t layers, const int32_t* dev_envs, int32_t count,
                    const uint8_t* dev_in, int64_t in_bytes, void* stream);
 
+/* Nearest-frontier moves: for every (env e, agent i) the first move of the
+ * reference's dijkstra_path_map(free_pad[i] - obst_pad[i], x + pad, y + pad)
+ * (dec_grid_rl.py:354-358) on the agent's own map over the pad-extended grid
+ * (pad = mc_config.pad; the pad ring is unexplored), on any handle at any
+ * time: the search of the dijkstra_input layer (pop order (cost, x, y), walk
+ * back by the first neighbour in the order +x, -x, +y, -y whose cost is one
+ * less) with the move as its output instead of obs layer 3.  d* is the cost
+ * of the path's end point, the nearest unexplored cell.
+ *
+ * dev_actions uint8 [B][N], required: with d* >= 1 the move from the agent's
+ * cell to the path's cost-1 cell as an MC_ACT_* code of mc_step (+x 0, +y 1,
+ * -x 2, -y 3); MC_ACT_STAY when the agent's own cell is unexplored (d* = 0)
+ * or no unexplored cell can be reached (empty path).
+ * dev_dist int32 [B][N], or NULL: d*; 0 and -1 in those two cases.
+ * dev_goal int32 [B][N][2], or NULL: the end point in padded-grid coordinates
+ * (extended coordinate minus pad; it can lie in the pad ring, x in [-pad,
+ * width + pad)); the agent's own cell when d* = -1 (dev_dist tells the cases
+ * apart).
+ *
+ * mc_frontier_setup (synchronous, idempotent) allocates what the call needs on
+ * this handle -- the work list of the full-map search and, for maps whose
+ * bitboards do not fit a workgroup's LDS, the HBM plane scratch (shared with a
+ * dijkstra_input handle's own) -- and picks the kernels as mc_create does for
+ * dijkstra_input (same LDS-fit rule, 32-bit cell index limit, scratch sizing
+ * and MARLCOV_DJ_FULL / MARLCOV_DJ_BIG / MARLCOV_DJ_BIG_GRID / MARLCOV_DJ_DEPTH);
+ * mc_layout.state_bytes counts the allocation from then on and mc_destroy frees
+ * it.  mc_frontier_variant names the choice as mc_dijkstra_variant does
+ * ("window+lds", "window+hbm", "lds", "hbm"; "" before setup).
+ *
+ * Call contract: as mc_export_maps.  Arguments are checked before anything is
+ * enqueued (MC_EINVAL naming a null env or dev_actions; MC_ESTATE before
+ * mc_frontier_setup); stream-ordered and asynchronous; no allocation, no
+ * synchronisation and no host read; fixed launch grids (capturable in a
+ * graph).  The call reads POS, FREE and OBST only and needs neither grids nor
+ * a beam table; it never writes env state, the obs buffers,
+ * MC_FIELD_DJ_LISTED or mc_env_launches.
+ *
+ * Added without raising MARLCOV_ABI_VERSION, like mc_export_maps. */
+enum { MC_ACT_STAY = 4 }; /* the no-op code the call writes (any of 4..254 is a no-op) */
+int mc_frontier_setup(void* env);
+const char* mc_frontier_variant(void* env);
+int mc_frontier_actions(void* env, uint8_t* dev_actions, int32_t* dev_dist, int32_t* dev_goal,
+                        void* stream);
+
 /* Synchronise `stream` and report (then clear) the device error word:
  * 1 = window, 4 = placement failed, 8 = bad injected cell, 32 = mc_copy_envs
  * index, 64 = mc_export_maps index, 128 = mc_import_maps index or robots

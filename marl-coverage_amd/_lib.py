@@ -19,6 +19,7 @@ SENSOR_LIDAR, SENSOR_SQUARE = 0, 1
 PARAM_DIST_CACHE_CELLS, PARAM_DIST_T, PARAM_DIST_MAX_ROWS = 0, 1, 2  # mc_build_param
 ACT_SENTINEL = 255
 ACT_NOOP = 4
+ACT_STAY = 4  # MC_ACT_STAY: the no-op code mc_frontier_actions writes
 
 # mc_export_maps layer bits, and their names in BatchCoverageEnv.global_state
 (MAP_GRID_NEG, MAP_GRID_POS, MAP_VISITED, MAP_OBST_ANY, MAP_ROBOTS, MAP_FREE, MAP_OBST) = (1 << b for b in range(7))
@@ -157,6 +158,9 @@ SIGNATURES = [
     ("mc_export_maps", ctypes.c_int, [_VP, ctypes.c_uint32, _I32, _VP, _I32, _VP, _I64, _VP]),
     ("mc_import_bytes", _I64, [_VP, ctypes.c_uint32, _I32]),
     ("mc_import_maps", ctypes.c_int, [_VP, ctypes.c_uint32, _VP, _I32, _VP, _I64, _VP]),
+    ("mc_frontier_setup", ctypes.c_int, [_VP]),
+    ("mc_frontier_variant", ctypes.c_char_p, [_VP]),
+    ("mc_frontier_actions", ctypes.c_int, [_VP, _VP, _VP, _VP, _VP]),
     ("mc_check", ctypes.c_int, [_VP, _VP]),
     ("mc_debug_stamps", ctypes.c_int, [_VP, _VP]),
     ("mc_set_dist_obs", ctypes.c_int, [_VP, _VP]),

@@ -513,6 +513,63 @@ class BatchCoverageEnv:
                                            t.data_ptr(), nbytes, self._stream()), "mc_import_maps")
 
     # ------------------------------------------------------------------
+    def _frontier_out(self, name, t, shape, dtype):
+        torch = self._torch
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=self.device)
+        if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype
+                or t.device != torch.device(self.device) or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {str(dtype).split('.')[-1]} tensor of shape {shape} "
+                             f"on {self.device}")
+        return t
+
+    def _frontier_setup(self):
+        if not getattr(self, "_frontier_ready", False):
+            _lib.check(self.lib.mc_frontier_setup(self._h), "mc_frontier_setup")
+            self._frontier_ready = True
+
+    def frontier_variant(self) -> str:
+        """The kernels of ``frontier`` / ``frontier_actions``
+        (mc_frontier_variant): "window+lds", "window+hbm", "lds", "hbm", or ""
+        before the first call."""
+        return self.lib.mc_frontier_variant(self._h).decode()
+
+    def frontier(self, actions=None, dist=None, goal=None):
+        """The nearest-frontier move of every agent on the current state
+        (mc_frontier_actions): the first step of the reference's
+        ``dijkstra_path_map`` on the agent's own map, whatever the env's
+        ``dijkstra_input``.  Returns ``(actions, dist, goal)``: uint8 [B, N]
+        action codes for ``step`` (``ACT_STAY`` where the agent's own cell is
+        unexplored or no unexplored cell can be reached), int32 [B, N] the
+        geodesic distance to that cell (0 and -1 in those two cases) and int32
+        [B, N, 2] the cell in padded-grid coordinates (it can lie in the
+        observation pad ring outside the grid; the agent's own cell when the
+        distance is -1).  The arguments are contiguous device tensors of those
+        shapes to fill instead of new ones.  The first call allocates the
+        search's work list on the handle (mc_frontier_setup); the call reads
+        positions and maps only and changes nothing of the env."""
+        torch = self._torch
+        B, N = self.num_envs, self.num_agents
+        actions = self._frontier_out("actions", actions, (B, N), torch.uint8)
+        dist = self._frontier_out("dist", dist, (B, N), torch.int32)
+        goal = self._frontier_out("goal", goal, (B, N, 2), torch.int32)
+        self._frontier_setup()
+        _lib.check(self.lib.mc_frontier_actions(self._h, actions.data_ptr(), dist.data_ptr(), goal.data_ptr(),
+                                                self._stream()), "mc_frontier_actions")
+        return actions, dist, goal
+
+    def frontier_actions(self, out=None):
+        """``frontier``'s action codes alone: uint8 [B, N] (``out``: a
+        contiguous uint8 device tensor of that shape to fill), the greedy
+        coverage baseline's ``env.step(env.frontier_actions())`` and the
+        expert label of every agent."""
+        out = self._frontier_out("out", out, (self.num_envs, self.num_agents), self._torch.uint8)
+        self._frontier_setup()
+        _lib.check(self.lib.mc_frontier_actions(self._h, out.data_ptr(), None, None, self._stream()),
+                   "mc_frontier_actions")
+        return out
+
+    # ------------------------------------------------------------------
     def _fork_index(self, src_index, source):
         """fork()'s arguments, checked: the int32 [B] device index tensor."""
         torch = self._torch

@@ -18,6 +18,7 @@
 #include "mc_env_select.h"
 #include "mc_export.h"
 #include "mc_fork.h"
+#include "mc_frontier.h"
 #include "mc_fuse.h"
 #include "mc_import.h"
 #include "mc_vistab.h"
@@ -42,6 +43,10 @@ hipError_t launch_dist(const State& s, int pad, int post, float* pre_out, float*
                        hipStream_t stream);
 hipError_t launch_dist_listed(const State& s, int pad, float* pre_out, float* dist_obs,
                               uint32_t* list, uint32_t* count, uint32_t* full, hipStream_t stream);
+hipError_t launch_frontier(const State& s, int pad, uint8_t* act, int32_t* dist, int32_t* goal,
+                           uint32_t* list, bool window, uint64_t* big, unsigned big_slots,
+                           hipStream_t stream);
+hipError_t frontier_allow_lds(size_t lds);
 size_t dist_lds_bytes(const State& s, int pad);
 size_t dist_static_lds_bytes();
 int dist_max_rows();
@@ -97,6 +102,14 @@ struct Env {
   bool dj_window = true;        // dijkstra_input: window kernel first (MARLCOV_DJ_FULL=1: off)
   uint64_t* dj_big = nullptr;   // dijkstra_input: the HBM kernel's plane scratch (null: the LDS kernel)
   unsigned dj_big_slots = 0;    // ... its slots = the HBM kernel's workgroups
+  // mc_frontier_setup: the frontier call's own count words and item list (dj_list's
+  // layout), its kernel choice, and the HBM kernel's scratch (a dijkstra_input
+  // handle's own where it has one: the work is stream-ordered)
+  bool fr_setup = false;
+  uint32_t* fr_list = nullptr;
+  bool fr_window = true;
+  uint64_t* fr_big = nullptr;
+  unsigned fr_big_slots = 0;
   size_t dt_lds = 0;  // dist_reward: LDS bytes of the distance kernel
   float* dist_pre = nullptr;  // dist_reward: [B][N][8] (library-owned)
   float* dist_obs = nullptr;  // dist_reward: caller's float32 [B][N][E][E]
@@ -1003,6 +1016,85 @@ const char* mc_dijkstra_variant(void* env) {
   if (!E->cfg.dijkstra_input) return "";
   if (E->dj_window) return E->dj_big ? "window+hbm" : "window+lds";
   return E->dj_big ? "hbm" : "lds";
+}
+
+static_assert(mc::kFrontierEinval == MC_EINVAL && mc::kFrontierEstate == MC_ESTATE && mc::kActStay == MC_ACT_STAY,
+              "mc_frontier.h restates marlcov.h's codes");
+
+// The kernel choice of mc_create's dijkstra_input block, for the frontier call.
+int mc_frontier_setup(void* env) {
+  Env* E = as_env(env);
+  const mc::FrontierCheck ck =
+      mc::frontier_check_setup(E, E ? E->s.Wp : 0, E ? E->s.Lp : 0, E ? E->cfg.pad : 0);
+  if (ck.rc) return fail(ck.rc, "%s", ck.msg);
+  if (E->fr_setup) return MC_OK;
+  const mc::State& s = E->s;
+  const int pad = E->cfg.pad;
+  HIP_TRY(hipSetDevice(E->device));
+  const size_t need = mc::dijkstra_lds_bytes(s, pad);
+  int maxlds = 0;
+  if (hipDeviceGetAttribute(&maxlds, hipDeviceAttributeMaxSharedMemoryPerBlock, E->device) != hipSuccess)
+    return fail(MC_EHIP, "mc_frontier_setup: cannot query the device's LDS per workgroup");
+  const char* fb = getenv("MARLCOV_DJ_BIG");
+  const bool big = need + 1024 > (size_t)maxlds || (fb && atoi(fb) == 1);
+  size_t added = 0;
+  uint64_t* scratch = nullptr;
+  unsigned slots = 0;
+  if (big && E->dj_big) {  // a dijkstra_input handle's scratch, sized by the same rule
+    scratch = E->dj_big;
+    slots = E->dj_big_slots;
+  } else if (big) {
+    slots = mc::dijkstra_big_slots(s, pad);
+    const size_t bytes = (size_t)slots * mc::dijkstra_big_slot_bytes(s, pad);
+    void* bq = nullptr;
+    if (dev_alloc(E, &bq, bytes) != MC_OK) {
+      std::string msg = g_err;
+      return fail(MC_EHIP, "mc_frontier_setup: %zu B of scratch (%u slots) for a %dx%d grid: %s", bytes, slots,
+                  E->cfg.width, E->cfg.length, msg.c_str());
+    }
+    scratch = (uint64_t*)bq;
+    added += bytes;
+  } else if (need > 65536) {
+    HIP_TRY(mc::frontier_allow_lds(need));
+  }
+  void* lq = nullptr;
+  const size_t list_bytes = ((size_t)s.B * s.N + 3) * 4;
+  if (dev_alloc(E, &lq, list_bytes) != MC_OK) {
+    std::string msg = g_err;
+    return fail(MC_EHIP, "mc_frontier_setup: item list: %s", msg.c_str());
+  }
+  added += list_bytes;
+  E->fr_list = (uint32_t*)lq;
+  E->fr_big = scratch;
+  E->fr_big_slots = slots;
+  const char* fo = getenv("MARLCOV_DJ_FULL");
+  E->fr_window = !(fo && atoi(fo) == 1);
+  E->lay.state_bytes += (int64_t)added;
+  HIP_TRY(hipDeviceSynchronize());  // the zeroed count words are there before any stream's first call
+  E->fr_setup = true;
+  return MC_OK;
+}
+
+const char* mc_frontier_variant(void* env) {
+  Env* E = as_env(env);
+  const mc::FrontierCheck ck = mc::frontier_check_variant(E);
+  if (ck.rc) {
+    fail(ck.rc, "%s", ck.msg);
+    return "";
+  }
+  if (!E->fr_setup) return "";
+  if (E->fr_window) return E->fr_big ? "window+hbm" : "window+lds";
+  return E->fr_big ? "hbm" : "lds";
+}
+
+int mc_frontier_actions(void* env, uint8_t* dev_actions, int32_t* dev_dist, int32_t* dev_goal, void* stream) {
+  Env* E = as_env(env);
+  const mc::FrontierCheck ck = mc::frontier_check_actions(E, dev_actions, E && E->fr_setup);
+  if (ck.rc) return fail(ck.rc, "%s", ck.msg);
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(mc::launch_frontier(E->s, E->cfg.pad, dev_actions, dev_dist, dev_goal, E->fr_list, E->fr_window,
+                              E->fr_big, E->fr_big_slots, (hipStream_t)stream));
+  return MC_OK;
 }
 
 int mc_set_env_grids(void* env, const int32_t* dev_env_grid, void* stream) {

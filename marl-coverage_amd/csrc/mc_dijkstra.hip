@@ -39,6 +39,10 @@
 // sx - j .. sx + j and the words of columns sy - j .. sy + j: the work grows
 // with d*^2, not with the map, and a plane word is initialised by the sweep
 // that first meets it.
+//
+// Every kernel's body is a template over a compile-time sink for its result:
+// the obs layer's crop (dijkstra_*_kernel) or the move of mc_frontier_actions
+// (frontier_*_kernel: action byte, d* and goal per item; mc_frontier.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -46,6 +50,7 @@
 #include <cstdlib>
 
 #include "mc_bitboard.h"
+#include "mc_frontier.h"
 
 namespace mc {
 
@@ -59,11 +64,42 @@ struct DjLds {
   uint64_t *tf, *to;  // the agent's free / obstacle tiles
 };
 
+// What a solve leaves behind (a compile-time choice of every kernel below; the
+// BFS and the end point are shared).  The crop sink records the path cells
+// inside the E x E crop: obs layer `layer` of obs_out.  The move sink keeps
+// only the walk's last step, the cell reached at j = 1, and one lane stores the
+// action byte, d* and the goal (mc_frontier_actions; dist / goal may be null).
+struct DjCropSink {
+  static constexpr bool kCrop = true;
+  int layer, Lc;
+  uint8_t* __restrict__ obs_out;
+};
+
+struct DjMoveSink {
+  static constexpr bool kCrop = false;
+  uint8_t* __restrict__ act;   // [B][N]
+  int32_t* __restrict__ dist;  // [B][N] or null
+  int32_t* __restrict__ goal;  // [B][N][2] or null
+  // item ea: d*, the start and the cost-1 cell (extended coordinates; any cell
+  // when d* < 1), the end point's extended cell index (when d* >= 0)
+  __device__ __forceinline__ void put(uint32_t ea, int dstar, int sx, int sy, int c1x, int c1y, int end,
+                                      int RY, int pad) const {
+    act[ea] = (uint8_t)(dstar >= 1 ? frontier_action(c1x - sx, c1y - sy) : kActStay);
+    if (dist) dist[ea] = dstar;
+    if (goal) {
+      int32_t gx, gy;
+      frontier_cell_xy(dstar >= 0 ? end : sx * RY + sy, RY, pad, &gx, &gy);
+      goal[2 * (size_t)ea] = gx;
+      goal[2 * (size_t)ea + 1] = gy;
+    }
+  }
+};
+
 }  // namespace
 
 // one (env, agent) on the whole map; every thread of the workgroup calls it
-__device__ __forceinline__ void dijkstra_full(const State& s, int pad, int layer, int Lc,
-                                              uint8_t* __restrict__ obs_out, int e, int a,
+template <class Sink>
+__device__ __forceinline__ void dijkstra_full(const State& s, int pad, const Sink& out, int e, int a,
                                               char* smem) {
   __shared__ int s_end[3], s_any[3];  // per BFS layer j: slot j % 3
   __shared__ uint32_t s_crop[32];
@@ -90,7 +126,9 @@ __device__ __forceinline__ void dijkstra_full(const State& s, int pad, int layer
   }
   const int sx = s.pos[((size_t)e * s.N + a) * 2] + pad;
   const int sy = s.pos[((size_t)e * s.N + a) * 2 + 1] + pad;
-  if (tid < 32) s_crop[tid] = 0;
+  if constexpr (Sink::kCrop) {
+    if (tid < 32) s_crop[tid] = 0;
+  }
   if (tid < 3) {
     s_end[tid] = INT32_MAX;
     s_any[tid] = 0;
@@ -172,15 +210,21 @@ __device__ __forceinline__ void dijkstra_full(const State& s, int pad, int layer
   // ---- walk back from the end point (first wave, lanes 0..3) --------------
   const int E = s.E, ego = s.ego;
   const int cx0 = sx - ego, cy0 = sy - ego;  // crop origin (dgrid coordinates)
+  int c1u = sx, c1v = sy;                    // move sink: the path's cost-1 cell
   if (dstar >= 0 && tid < 64) {
     int cu = end / RY, cv = end - (end / RY) * RY;
     int j = dstar;
     const int du = tid == 0 ? 1 : (tid == 1 ? -1 : 0);
     const int dv = tid == 2 ? 1 : (tid == 3 ? -1 : 0);
     for (;;) {
-      if (tid == 0) {
-        const int r = cu - cx0, c = cv - cy0;
-        if (r >= 0 && r < E && c >= 0 && c < E) s_crop[r] |= 1u << c;
+      if constexpr (Sink::kCrop) {
+        if (tid == 0) {
+          const int r = cu - cx0, c = cv - cy0;
+          if (r >= 0 && r < E && c >= 0 && c < E) s_crop[r] |= 1u << c;
+        }
+      } else if (j == 1) {
+        c1u = cu;
+        c1v = cv;
       }
       if (j == 0) break;
       const int nu = cu + du, nv = cv + dv;
@@ -201,12 +245,17 @@ __device__ __forceinline__ void dijkstra_full(const State& s, int pad, int layer
       --j;
     }
   }
-  __syncthreads();
-  // ---- obs layer `layer` of agent a: the path cells inside the crop ----------
-  uint8_t* dst = obs_out + (((size_t)e * s.N + a) * Lc + layer) * E * E;
-  for (int i = tid; i < E * E; i += kDjThreads) {
-    const int r = i / E, c = i - r * E;
-    dst[i] = (uint8_t)((s_crop[r] >> c) & 1u);
+  if constexpr (Sink::kCrop) {
+    __syncthreads();
+    // ---- obs layer `layer` of agent a: the path cells inside the crop ----------
+    uint8_t* dst = out.obs_out + (((size_t)e * s.N + a) * out.Lc + out.layer) * E * E;
+    for (int i = tid; i < E * E; i += kDjThreads) {
+      const int r = i / E, c = i - r * E;
+      dst[i] = (uint8_t)((s_crop[r] >> c) & 1u);
+    }
+  } else {
+    // ---- the move: lane 0 of the walk's wave holds the cost-1 cell ---------------
+    if (tid == 0) out.put((uint32_t)e * (uint32_t)s.N + (uint32_t)a, dstar, sx, sy, c1u, c1v, end, RY, pad);
   }
 }
 
@@ -216,18 +265,17 @@ __device__ __forceinline__ void dijkstra_full(const State& s, int pad, int layer
 // count[0] = entries, count[1] = workgroups done: the last workgroup to
 // finish zeroes both for the next step's window kernel (every workgroup has
 // read the entry count before it counts itself done) and keeps the entry
-// count in count[2] (MC_FIELD_DJ_LISTED).
-__global__ __launch_bounds__(kDjThreads) void dijkstra_kernel(State s, int pad, int layer, int Lc,
-                                                              uint8_t* __restrict__ obs_out,
-                                                              const uint32_t* __restrict__ list,
-                                                              uint32_t* __restrict__ count) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+// count in count[2] (MC_FIELD_DJ_LISTED for the obs layer's list; the frontier
+// call brings count words and a list of its own).
+template <class Sink>
+__device__ __forceinline__ void dijkstra_items(const State& s, int pad, const Sink& out,
+                                               const uint32_t* __restrict__ list,
+                                               uint32_t* __restrict__ count, char* smem) {
   const uint32_t n_items = list ? __atomic_load_n(count, __ATOMIC_RELAXED) : (uint32_t)gridDim.x;
   for (uint32_t it = blockIdx.x; it < n_items; it += (list ? gridDim.x : n_items)) {
     __syncthreads();  // the previous item's LDS reads are done
     const uint32_t ea = list ? list[it] : it;
-    dijkstra_full(s, pad, layer, Lc, obs_out, (int)(ea / (uint32_t)s.N), (int)(ea % (uint32_t)s.N),
-                  smem);
+    dijkstra_full(s, pad, out, (int)(ea / (uint32_t)s.N), (int)(ea % (uint32_t)s.N), smem);
   }
   if (list && threadIdx.x == 0) {
     if (n_items == 0) {  // nothing listed: nothing to reset (every workgroup read 0)
@@ -240,6 +288,22 @@ __global__ __launch_bounds__(kDjThreads) void dijkstra_kernel(State s, int pad, 
       }
     }
   }
+}
+
+__global__ __launch_bounds__(kDjThreads) void dijkstra_kernel(State s, int pad, int layer, int Lc,
+                                                              uint8_t* __restrict__ obs_out,
+                                                              const uint32_t* __restrict__ list,
+                                                              uint32_t* __restrict__ count) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  dijkstra_items(s, pad, DjCropSink{layer, Lc, obs_out}, list, count, smem);
+}
+
+// ... with the move sink, over the frontier call's own list (mc_frontier_actions)
+__global__ __launch_bounds__(kDjThreads) void frontier_kernel(State s, int pad, DjMoveSink out,
+                                                              const uint32_t* __restrict__ list,
+                                                              uint32_t* __restrict__ count) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  dijkstra_items(s, pad, out, list, count, smem);
 }
 
 // ---- window kernel ---------------------------------------------------------
@@ -281,11 +345,10 @@ __device__ __forceinline__ uint64_t pred(uint64_t k0, uint64_t k1, uint64_t k2, 
 // is tiles [tx - 4, tx + 4) x [ty - 4, ty + 4) of the robot's tile (tx, ty),
 // i.e. map rows X0 = 8 (tx - 4) .. X0 + 63 and columns Y0 .. Y0 + 63; bit c of
 // a row word is column Y0 + c.  depth: the exact layers (kDjWinDepth).
-__global__ __launch_bounds__(64) void dijkstra_window_kernel(State s, int pad, int layer, int Lc,
-                                                             uint8_t* __restrict__ obs_out,
-                                                             uint32_t* __restrict__ list,
-                                                             uint32_t* __restrict__ count,
-                                                             int depth) {
+template <class Sink>
+__device__ __forceinline__ void dijkstra_window(const State& s, int pad, const Sink& out,
+                                                uint32_t* __restrict__ list,
+                                                uint32_t* __restrict__ count, int depth) {
   __shared__ uint8_t s_rows[2][64 * 8];  // free / obstacle window rows (tile transpose)
   const uint32_t ea = blockIdx.x;
   const int r = threadIdx.x;
@@ -389,6 +452,7 @@ __global__ __launch_bounds__(64) void dijkstra_window_kernel(State s, int pad, i
   const int E = s.E, ego = s.ego;
   const int cr0 = rs - ego, cc0 = cs - ego;  // crop origin (window coordinates)
   uint32_t crop = 0;
+  int c1r = rs, c1c = cs;  // move sink: the path's cost-1 cell (window coordinates)
   if (dstar >= 0) {
     const uint64_t k1 = m0, k2 = m1, k0 = ~ob & valid & ~avail & ~m0 & ~m1;  // reached, cost = 0 mod 3
     const uint64_t px_ = pred(k0, k1, k2, row_below(k0), row_below(k1), row_below(k2));
@@ -398,19 +462,48 @@ __global__ __launch_bounds__(64) void dijkstra_window_kernel(State s, int pad, i
     const uint64_t d0 = (~px_ & mx_) | (d1 & ~py_);
     int cu = er, cv = ec;
     for (int j = dstar;; --j) {
-      const int kr = cu - cr0, kc = cv - cc0;
-      if ((unsigned)kr < (unsigned)E && (unsigned)kc < (unsigned)E && r == kr) crop |= 1u << kc;
+      if constexpr (Sink::kCrop) {
+        const int kr = cu - cr0, kc = cv - cc0;
+        if ((unsigned)kr < (unsigned)E && (unsigned)kc < (unsigned)E && r == kr) crop |= 1u << kc;
+      } else if (j == 1) {
+        c1r = cu;
+        c1c = cv;
+      }
       if (j == 0) break;
       const int q = (int)(2 * lane_bit(d1, cu, cv) + lane_bit(d0, cu, cv));
       cu += q == 0 ? 1 : (q == 1 ? -1 : 0);
       cv += q == 2 ? 1 : (q == 3 ? -1 : 0);
     }
   }
-  // ---- obs layer `layer`: crop row k = window row rs - ego + k ------------------
-  if (r < E) {
-    uint8_t* dst = obs_out + ((size_t)ea * Lc + layer) * E * E + (size_t)r * E;
-    for (int c = 0; c < E; ++c) dst[c] = (uint8_t)((crop >> c) & 1u);
+  if constexpr (Sink::kCrop) {
+    // ---- obs layer `layer`: crop row k = window row rs - ego + k ------------------
+    if (r < E) {
+      uint8_t* dst = out.obs_out + ((size_t)ea * out.Lc + out.layer) * E * E + (size_t)r * E;
+      for (int c = 0; c < E; ++c) dst[c] = (uint8_t)((crop >> c) & 1u);
+    }
+  } else {
+    // ---- the move: the walk is wave-uniform, lane 0 stores it (extended
+    // coordinates: window cell (k, c) is padded-grid cell (X0 + k, Y0 + c))
+    const int RY = s.Lp + 2 * pad;
+    if (r == 0)
+      out.put(ea, dstar, px + pad, py + pad, X0 + c1r + pad, Y0 + c1c + pad,
+              frontier_cell_index(X0 + er, Y0 + ec, RY, pad), RY, pad);
   }
+}
+
+__global__ __launch_bounds__(64) void dijkstra_window_kernel(State s, int pad, int layer, int Lc,
+                                                             uint8_t* __restrict__ obs_out,
+                                                             uint32_t* __restrict__ list,
+                                                             uint32_t* __restrict__ count,
+                                                             int depth) {
+  dijkstra_window(s, pad, DjCropSink{layer, Lc, obs_out}, list, count, depth);
+}
+
+__global__ __launch_bounds__(64) void frontier_window_kernel(State s, int pad, DjMoveSink out,
+                                                             uint32_t* __restrict__ list,
+                                                             uint32_t* __restrict__ count,
+                                                             int depth) {
+  dijkstra_window(s, pad, out, list, count, depth);
 }
 
 // ---- big kernel: the planes in HBM -----------------------------------------
@@ -446,8 +539,8 @@ __device__ __forceinline__ DjBand dj_band(int sx, int sy, int j, int RX, int RY)
 // band 0: layer j writes nxt over all of band j, which is all that layer
 // j + 1 reads of it.  Threads hand words to each other only across the
 // __syncthreads() that ends a layer (one workgroup owns the slot).
-__device__ __forceinline__ void dijkstra_big(const State& s, int pad, int layer, int Lc,
-                                             uint8_t* __restrict__ obs_out, int e, int a,
+template <class Sink>
+__device__ __forceinline__ void dijkstra_big(const State& s, int pad, const Sink& out, int e, int a,
                                              uint64_t* planes) {
   __shared__ int s_end[3], s_any[3], s_tg0;  // per BFS layer j: slot j % 3; the start cell's target bit
   __shared__ uint32_t s_crop[32];
@@ -467,7 +560,9 @@ __device__ __forceinline__ void dijkstra_big(const State& s, int pad, int layer,
   const int sx = s.pos[((size_t)e * s.N + a) * 2] + pad;
   const int sy = s.pos[((size_t)e * s.N + a) * 2 + 1] + pad;
   const uint64_t last = (RY & 63) ? low_mask(RY & 63) : ~0ull;
-  if (tid < 32) s_crop[tid] = 0;
+  if constexpr (Sink::kCrop) {
+    if (tid < 32) s_crop[tid] = 0;
+  }
   if (tid < 3) {
     s_end[tid] = INT32_MAX;
     s_any[tid] = 0;
@@ -578,15 +673,21 @@ __device__ __forceinline__ void dijkstra_big(const State& s, int pad, int layer,
   // neighbour outside the last band was never reached
   const int E = s.E, ego = s.ego;
   const int cx0 = sx - ego, cy0 = sy - ego;  // crop origin (dgrid coordinates)
+  int c1u = sx, c1v = sy;                    // move sink: the path's cost-1 cell
   if (dstar >= 0 && tid < 64) {
     int cu = end / RY, cv = end - (end / RY) * RY;
     int j = dstar;
     const int du = tid == 0 ? 1 : (tid == 1 ? -1 : 0);
     const int dv = tid == 2 ? 1 : (tid == 3 ? -1 : 0);
     for (;;) {
-      if (tid == 0) {
-        const int r = cu - cx0, c = cv - cy0;
-        if (r >= 0 && r < E && c >= 0 && c < E) s_crop[r] |= 1u << c;
+      if constexpr (Sink::kCrop) {
+        if (tid == 0) {
+          const int r = cu - cx0, c = cv - cy0;
+          if (r >= 0 && r < E && c >= 0 && c < E) s_crop[r] |= 1u << c;
+        }
+      } else if (j == 1) {
+        c1u = cu;
+        c1v = cv;
       }
       if (j == 0) break;
       const int nu = cu + du, nv = cv + dv;
@@ -608,31 +709,34 @@ __device__ __forceinline__ void dijkstra_big(const State& s, int pad, int layer,
       --j;
     }
   }
-  __syncthreads();
-  // ---- obs layer `layer` of agent a: the path cells inside the crop ----------
-  uint8_t* dst = obs_out + (((size_t)e * s.N + a) * Lc + layer) * E * E;
-  for (int i = tid; i < E * E; i += kDjThreads) {
-    const int r = i / E, c = i - r * E;
-    dst[i] = (uint8_t)((s_crop[r] >> c) & 1u);
+  if constexpr (Sink::kCrop) {
+    __syncthreads();
+    // ---- obs layer `layer` of agent a: the path cells inside the crop ----------
+    uint8_t* dst = out.obs_out + (((size_t)e * s.N + a) * out.Lc + out.layer) * E * E;
+    for (int i = tid; i < E * E; i += kDjThreads) {
+      const int r = i / E, c = i - r * E;
+      dst[i] = (uint8_t)((s_crop[r] >> c) & 1u);
+    }
+  } else {
+    // ---- the move: lane 0 of the walk's wave holds the cost-1 cell ---------------
+    if (tid == 0) out.put((uint32_t)e * (uint32_t)s.N + (uint32_t)a, dstar, sx, sy, c1u, c1v, end, RY, pad);
   }
 }
 
 // dijkstra_kernel's role and list protocol (count[0..2] as there) with the
 // planes in HBM: workgroup blockIdx.x owns scratch slot blockIdx.x and strides
 // over the listed items (list == nullptr: over all n_all (env, agent) items).
-__global__ __launch_bounds__(kDjThreads) void dijkstra_big_kernel(State s, int pad, int layer, int Lc,
-                                                                  uint8_t* __restrict__ obs_out,
-                                                                  const uint32_t* __restrict__ list,
-                                                                  uint32_t* __restrict__ count,
-                                                                  uint32_t n_all, uint64_t* scratch,
-                                                                  size_t slot_words) {
+template <class Sink>
+__device__ __forceinline__ void dijkstra_big_items(const State& s, int pad, const Sink& out,
+                                                   const uint32_t* __restrict__ list,
+                                                   uint32_t* __restrict__ count, uint32_t n_all,
+                                                   uint64_t* scratch, size_t slot_words) {
   uint64_t* planes = scratch + (size_t)blockIdx.x * slot_words;
   const uint32_t n_items = list ? __atomic_load_n(count, __ATOMIC_RELAXED) : n_all;
   for (uint32_t it = blockIdx.x; it < n_items; it += gridDim.x) {
     __syncthreads();  // the previous item's reads (LDS and slot) are done
     const uint32_t ea = list ? list[it] : it;
-    dijkstra_big(s, pad, layer, Lc, obs_out, (int)(ea / (uint32_t)s.N), (int)(ea % (uint32_t)s.N),
-                 planes);
+    dijkstra_big(s, pad, out, (int)(ea / (uint32_t)s.N), (int)(ea % (uint32_t)s.N), planes);
   }
   if (list && threadIdx.x == 0) {
     if (n_items == 0) {  // nothing listed: nothing to reset (every workgroup read 0)
@@ -645,6 +749,23 @@ __global__ __launch_bounds__(kDjThreads) void dijkstra_big_kernel(State s, int p
       }
     }
   }
+}
+
+__global__ __launch_bounds__(kDjThreads) void dijkstra_big_kernel(State s, int pad, int layer, int Lc,
+                                                                  uint8_t* __restrict__ obs_out,
+                                                                  const uint32_t* __restrict__ list,
+                                                                  uint32_t* __restrict__ count,
+                                                                  uint32_t n_all, uint64_t* scratch,
+                                                                  size_t slot_words) {
+  dijkstra_big_items(s, pad, DjCropSink{layer, Lc, obs_out}, list, count, n_all, scratch, slot_words);
+}
+
+__global__ __launch_bounds__(kDjThreads) void frontier_big_kernel(State s, int pad, DjMoveSink out,
+                                                                  const uint32_t* __restrict__ list,
+                                                                  uint32_t* __restrict__ count,
+                                                                  uint32_t n_all, uint64_t* scratch,
+                                                                  size_t slot_words) {
+  dijkstra_big_items(s, pad, out, list, count, n_all, scratch, slot_words);
 }
 
 size_t dijkstra_lds_bytes(const State& s, int pad) {
@@ -676,22 +797,52 @@ unsigned dijkstra_big_slots(const State& s, int pad) {
 // the full map (the parity tests' second mode).  big: the big kernel's scratch
 // of big_slots slots (mc_create: the LDS bitboards do not fit, or
 // MARLCOV_DJ_BIG=1) -- it then takes the full kernel's place; nullptr: the
-// full kernel.
-hipError_t launch_dijkstra(const State& s, int pad, int layer, int Lc, uint8_t* obs,
-                           uint32_t* list, bool window, uint64_t* big, unsigned big_slots,
-                           hipStream_t stream) {
+// full kernel.  (launch_solve below, for either sink.)
+namespace {
+
+// the three kernels of each sink (list == nullptr: every item, no protocol)
+void run_window(const DjCropSink& o, unsigned items, hipStream_t st, const State& s, int pad, uint32_t* list,
+                int depth) {
+  hipLaunchKernelGGL(dijkstra_window_kernel, dim3(items), dim3(64), 0, st, s, pad, o.layer, o.Lc, o.obs_out,
+                     list + 3, list, depth);
+}
+void run_window(const DjMoveSink& o, unsigned items, hipStream_t st, const State& s, int pad, uint32_t* list,
+                int depth) {
+  hipLaunchKernelGGL(frontier_window_kernel, dim3(items), dim3(64), 0, st, s, pad, o, list + 3, list, depth);
+}
+void run_full(const DjCropSink& o, unsigned grid, size_t lds, hipStream_t st, const State& s, int pad,
+              uint32_t* list) {
+  hipLaunchKernelGGL(dijkstra_kernel, dim3(grid), dim3(kDjThreads), lds, st, s, pad, o.layer, o.Lc, o.obs_out,
+                     (const uint32_t*)(list ? list + 3 : nullptr), list);
+}
+void run_full(const DjMoveSink& o, unsigned grid, size_t lds, hipStream_t st, const State& s, int pad,
+              uint32_t* list) {
+  hipLaunchKernelGGL(frontier_kernel, dim3(grid), dim3(kDjThreads), lds, st, s, pad, o,
+                     (const uint32_t*)(list ? list + 3 : nullptr), list);
+}
+void run_big(const DjCropSink& o, unsigned slots, hipStream_t st, const State& s, int pad, uint32_t* list,
+             unsigned items, uint64_t* big, size_t slot_words) {
+  hipLaunchKernelGGL(dijkstra_big_kernel, dim3(slots), dim3(kDjThreads), 0, st, s, pad, o.layer, o.Lc, o.obs_out,
+                     (const uint32_t*)(list ? list + 3 : nullptr), list, items, big, slot_words);
+}
+void run_big(const DjMoveSink& o, unsigned slots, hipStream_t st, const State& s, int pad, uint32_t* list,
+             unsigned items, uint64_t* big, size_t slot_words) {
+  hipLaunchKernelGGL(frontier_big_kernel, dim3(slots), dim3(kDjThreads), 0, st, s, pad, o,
+                     (const uint32_t*)(list ? list + 3 : nullptr), list, items, big, slot_words);
+}
+
+template <class Sink>
+hipError_t launch_solve(const State& s, int pad, const Sink& out, uint32_t* list, bool window, uint64_t* big,
+                        unsigned big_slots, hipStream_t stream) {
   const unsigned items = (unsigned)((size_t)s.B * s.N);
   // dynamic LDS of the full kernel / words of a scratch slot of the big kernel
   const size_t lds = big ? 0 : dijkstra_lds_bytes(s, pad);
   const size_t slot_words = big ? dijkstra_big_slot_bytes(s, pad) / 8 : 0;
   if (!window) {
     if (big)  // a fixed grid over every item: a slot per workgroup
-      hipLaunchKernelGGL(dijkstra_big_kernel, dim3(big_slots), dim3(kDjThreads), 0, stream, s, pad,
-                         layer, Lc, obs, (const uint32_t*)nullptr, (uint32_t*)nullptr, items, big,
-                         slot_words);
+      run_big(out, big_slots, stream, s, pad, nullptr, items, big, slot_words);
     else
-      hipLaunchKernelGGL(dijkstra_kernel, dim3(items), dim3(kDjThreads), lds, stream, s, pad, layer,
-                         Lc, obs, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+      run_full(out, items, lds, stream, s, pad, nullptr);
     return hipGetLastError();
   }
   static const int depth = [] {  // MARLCOV_DJ_DEPTH: fewer exact layers (diagnostics, A/B)
@@ -699,11 +850,9 @@ hipError_t launch_dijkstra(const State& s, int pad, int layer, int Lc, uint8_t* 
     const int d = v ? atoi(v) : kDjWinDepth;
     return d >= 0 && d < kDjWinDepth ? d - d % 3 : kDjWinDepth;  // whole trips of 3 layers
   }();
-  hipLaunchKernelGGL(dijkstra_window_kernel, dim3(items), dim3(64), 0, stream, s, pad, layer, Lc,
-                     obs, list + 3, list, depth);
+  run_window(out, items, stream, s, pad, list, depth);
   if (big) {  // the listed items: the big kernel's fixed grid strides over the count
-    hipLaunchKernelGGL(dijkstra_big_kernel, dim3(big_slots), dim3(kDjThreads), 0, stream, s, pad,
-                       layer, Lc, obs, (const uint32_t*)(list + 3), list, items, big, slot_words);
+    run_big(out, big_slots, stream, s, pad, list, items, big, slot_words);
     return hipGetLastError();
   }
   // the listed items: a fixed grid (hipGraph capture) strides over the count
@@ -712,10 +861,31 @@ hipError_t launch_dijkstra(const State& s, int pad, int layer, int Lc, uint8_t* 
     const int g = v ? atoi(v) : 0;
     return g > 0 && g <= 4096 ? (unsigned)g : kDjFullGrid;
   }();
-  const unsigned grid = items < full_grid ? items : full_grid;
-  hipLaunchKernelGGL(dijkstra_kernel, dim3(grid), dim3(kDjThreads), lds, stream, s, pad, layer, Lc,
-                     obs, (const uint32_t*)(list + 3), list);
+  run_full(out, items < full_grid ? items : full_grid, lds, stream, s, pad, list);
   return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_dijkstra(const State& s, int pad, int layer, int Lc, uint8_t* obs,
+                           uint32_t* list, bool window, uint64_t* big, unsigned big_slots,
+                           hipStream_t stream) {
+  return launch_solve(s, pad, DjCropSink{layer, Lc, obs}, list, window, big, big_slots, stream);
+}
+
+// mc_frontier_actions: the same launches with the move sink, over the frontier
+// call's own list (same layout); dist / goal may be null
+hipError_t launch_frontier(const State& s, int pad, uint8_t* act, int32_t* dist, int32_t* goal,
+                           uint32_t* list, bool window, uint64_t* big, unsigned big_slots,
+                           hipStream_t stream) {
+  return launch_solve(s, pad, DjMoveSink{act, dist, goal}, list, window, big, big_slots, stream);
+}
+
+// mc_frontier_setup: the full kernel's dynamic LDS past 64 KiB needs the
+// attribute once (mc_capi.hip sets it on dijkstra_kernel at every step)
+hipError_t frontier_allow_lds(size_t lds) {
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(&frontier_kernel),
+                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
 
 }  // namespace mc

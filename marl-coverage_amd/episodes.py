@@ -42,6 +42,21 @@ def random_policy(env, seed=0):
     return pi
 
 
+def frontier_policy(env):
+    """The nearest-frontier controller (the reference's DijkstraFrontier
+    example) as a batched policy: every agent steps along the shortest path to
+    the nearest cell its own map has not explored
+    (``BatchCoverageEnv.frontier_actions``).  It reads the env's state, not
+    the observation it is handed."""
+    if hasattr(env, "planes"):  # BatchSuperGridEnv
+        raise ValueError("frontier_policy: a BatchSuperGridEnv has no per-agent maps to plan on "
+                         "(BatchCoverageEnv only)")
+
+    def pi(_obs):
+        return env.frontier_actions()
+    return pi
+
+
 def _record_fields(env):
     """(get_state function, episode-record fields) of a batch env type."""
     if hasattr(env, "planes"):  # BatchSuperGridEnv
