@@ -114,6 +114,11 @@ struct EnvCfg {
   // to store_tiles instead of computing it twice (two VGPRs per lane: the
   // C4 bench kernel, at 128, has none to give)
   static constexpr bool KEEP_GT = LANEK;
+  // the fused loop also carries the env head (HeadK, mc_env_step.h: the robot
+  // cells, the env's counters, the next step's action bytes) instead of loading
+  // back what the wave stored a step earlier: the one-wave table kernels only
+  // (the march rows have no VGPRs to give: 13 more words cost them a wave)
+  static constexpr bool CARRY = LANEK && VISTAB;
 };
 
 // ---- the instantiations: X(NT, EPW, word, shape, public name), one row per

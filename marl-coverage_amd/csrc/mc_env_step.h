@@ -37,6 +37,7 @@
 
 #include "mc_device.h"
 #include "mc_env_select.h"
+#include "mc_fuse.h"
 #include "mc_vistab.h"
 
 namespace mc {
@@ -214,6 +215,36 @@ struct Ctx : EnvCfg<NT_, EPW_, WT_, SH_> {
 // in its VGPR, and nothing derived from it is loop-invariant to the compiler.
 struct LaneK {
   uint32_t ob;  // the lane's ObsRoles, packed
+};
+
+// The env head the fused loop carries from step to step (EnvCfg::CARRY): what
+// round trip 1 of step k + 1 would load, as step k computed it -- every one of
+// them but the action bytes is a value this wave stored a step earlier, and
+// loading it again makes the step wait for its own stores to reach L2 and come
+// back.  One 32-bit word per member and lane, passed through an empty asm at
+// the top of every iteration like LaneK's.
+//
+// The invalidation rule.  Every store of a step stays: pos, rec, moved and the
+// tiles are written in every step exactly as without the carry, so memory is
+// authoritative at every step boundary -- chunk boundaries, get_state, copies,
+// imports and exports between calls, the dist and dijkstra kernels and step 0
+// of the next launch need nothing.  The words live within one launch.  A
+// slot's `ok` is set only by a step that took `active && !do_reset`; any other
+// path (a reset in the step or by sentinel, a sentinel step without auto-reset,
+// reset_req, MODE_RESET, an env_mask) leaves it clear, and a wave with a clear
+// flag in either slot takes round trip 1's loads for both slots, which is
+// right for both because memory is authoritative.  An idle slot (the second
+// slot of a short last wave) keeps `ok` set and the words of env B - 1 as its
+// wave last loaded them: real cells of a real env, whatever their age, for the
+// clamped address arithmetic of its obs-only path; it stores nothing.
+struct HeadK {
+  uint32_t xy;                  // the lane's robot (sub % N): its cell, x | y << 16
+  uint32_t act, act0;           // the next step's action byte of that robot, and of agent 0
+  uint32_t grid, numfree;       // env_grid and numfree[env_grid]: they change only at a reset
+  uint32_t moved_lo, moved_hi;  // EnvRec::moved
+  uint32_t free_cnt, vis_cnt, currstep;
+  uint32_t dt_lo, dt_hi;        // EnvRec::done_thresh
+  uint32_t ok;                  // the words are the slot's state after the step (see above)
 };
 
 // broadcast lane (lane0 + i)'s value of v to the slot
@@ -2212,8 +2243,12 @@ constexpr int env_min_waves() {
 // One step (or the reset) of the slot's env: step k of the launch, with io the
 // launch's buffers as step k sees them (io_at_step).  `valid`: the slot has an
 // env (a short last workgroup's idle slot writes nothing, in any step).
+// Hd (CT::CARRY): the carried env head -- every step refills it, and the loop
+// copy builds round trip 1's results from it when no slot of the wave is stale
+// (HeadK has the rule).
 template <class CT, bool LOOP = false>
-__device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool valid, const int k) {
+__device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool valid, const int k,
+                                         [[maybe_unused]] HeadK& Hd) {
   using WT = typename CT::WT;
   using SH = typename CT::SH;
   constexpr int NT = CT::NT, EPW = CT::EPW;
@@ -2237,11 +2272,49 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
   const uint8_t* ab = is_step ? io.actions : reinterpret_cast<const uint8_t*>(s.pos);
   const uint32_t eN = (uint32_t)e * (uint32_t)N;
   const uint8_t* mb = io.env_mask != nullptr ? io.env_mask + e : reinterpret_cast<const uint8_t*>(s.pos);
-  const int2 p0 = el<O32>(reinterpret_cast<const int2*>(s.pos), eN + ag);
-  const int act_raw = el<O32>(ab, is_step ? eN + ag : 0), act0_raw = el<O32>(ab, is_step ? eN : 0);
-  const int req_raw = mb[0];
-  const RecLo rl0 = rec_lo(el<O32>(s.rec, e));  // the env's record: two 16-byte loads
-  const RecHi rh0 = rec_hi(el<O32>(s.rec, e));
+  // (CARRY, loop copy: none of these loads when every slot of the wave holds
+  // its head from the step before -- a wave-uniform test)
+  [[maybe_unused]] bool carried = false;
+  if constexpr (CT::CARRY && LOOP) carried = __ballot(Hd.ok == 0) == 0 && io.env_mask == nullptr && is_step;
+  int2 p0;
+  int act_raw, act0_raw, req_raw;
+  RecLo rl0;
+  RecHi rh0;
+  if (CT::CARRY && LOOP && carried) {
+    p0 = make_int2((int)(Hd.xy & 0xFFFFu), (int)(Hd.xy >> 16));
+    act_raw = (int)Hd.act;
+    act0_raw = (int)Hd.act0;
+    req_raw = 0;  // (no env_mask)
+    rl0 = RecLo{__hiloint2double((int)Hd.dt_hi, (int)Hd.dt_lo), Hd.free_cnt, Hd.vis_cnt};
+    rh0 = RecHi{(int32_t)Hd.currstep, (int32_t)Hd.grid, (uint64_t)Hd.moved_lo | ((uint64_t)Hd.moved_hi << 32)};
+  } else {
+    p0 = el<O32>(reinterpret_cast<const int2*>(s.pos), eN + ag);
+    act_raw = el<O32>(ab, is_step ? eN + ag : 0);
+    act0_raw = el<O32>(ab, is_step ? eN : 0);
+    req_raw = mb[0];
+    rl0 = rec_lo(el<O32>(s.rec, e));  // the env's record: two 16-byte loads
+    rh0 = rec_hi(el<O32>(s.rec, e));
+    if constexpr (CT::CARRY) {
+      // the head as loaded: what a slot that is not active in this step keeps
+      // (an idle slot for good; the active path below refills every word)
+      Hd.xy = (uint32_t)p0.x | ((uint32_t)p0.y << 16);
+      Hd.act = (uint32_t)act_raw;
+      Hd.act0 = (uint32_t)act0_raw;
+      Hd.grid = (uint32_t)rh0.env_grid;
+      Hd.moved_lo = (uint32_t)rh0.moved;
+      Hd.moved_hi = (uint32_t)(rh0.moved >> 32);
+      Hd.free_cnt = rl0.free_cnt;
+      Hd.vis_cnt = rl0.vis_cnt;
+      Hd.currstep = (uint32_t)rh0.currstep;
+      Hd.dt_lo = (uint32_t)__double2loint(rl0.done_thresh);
+      Hd.dt_hi = (uint32_t)__double2hiint(rl0.done_thresh);
+      // the loads land here, inside the branch (vmcnt(0); a real s_waitcnt,
+      // which the compiler's own wait insertion sees): after the join it
+      // would place the wait on both paths, and on the carried path a
+      // vmcnt(0) waits for nothing but the previous step's stores
+      __builtin_amdgcn_s_waitcnt(0x0F70);
+    }
+  }
   const int g0 = rh0.env_grid;
   const uint64_t moved0 = rh0.moved;
   const uint32_t free_old = rl0.free_cnt, vis_old = rl0.vis_cnt;
@@ -2270,10 +2343,15 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
   int4 chd = make_int4(-1, 0, 0, 0);
   int2 chb = make_int2(0, 0);
   if (s.dist) mwv = reinterpret_cast<const int2*>(s.dist_mw)[eN + agd];
-  if (s.dist_ch) {
-    const int4* hp = reinterpret_cast<const int4*>(s.dist_ch + ((size_t)eN + agd) * 8);
-    chd = hp[0];
-    chb = *reinterpret_cast<const int2*>(hp + 1);
+  // (CARRY: shapes without dist_reward, which have no cache -- and no load of
+  // it after the join of the carried and the loading path, see there)
+  static_assert(!CT::CARRY || (SH::EGO > 0 && SH::DS == 0 && CT::FRONT && CT::VISTAB), "the carried head's kernels");
+  if constexpr (!CT::CARRY) {
+    if (s.dist_ch) {
+      const int4* hp = reinterpret_cast<const int4*>(s.dist_ch + ((size_t)eN + agd) * 8);
+      chd = hp[0];
+      chb = *reinterpret_cast<const int2*>(hp + 1);
+    }
   }
   if constexpr (!CT::VISTAB) zero_marks(s, C);  // overlaps the round trip (VISTAB: no mark plane)
   // every result is needed below: keep the compiler from sinking a load into
@@ -2296,6 +2374,8 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
   const bool reset_req = valid && !is_step && req != 0;
   const bool active = valid && is_step && !sentinel;
   const bool sent_reset = sentinel && s.auto_reset;  // a sentinel's done resets too
+  // the slot's head is stale after this step unless the active path says otherwise
+  if constexpr (CT::CARRY) Hd.ok = valid ? 0u : 1u;
   // dist_reward: this lane's agent (C.sub < N) goes to the full transform's list
   bool dlist = false;
   if (C.sub < N) {
@@ -2339,6 +2419,8 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
     STAMP(1);
     Items<KI> I;
     [[maybe_unused]] VisTiles<KI> V;  // VISTAB: the items' tiles of their robots' records, in flight
+    // CARRY: the next step's action bytes, in flight during this step, and the lane's robot's cell after the moves
+    [[maybe_unused]] uint32_t act_next = 0, act0_next = 0, xy_next = 0;
     if constexpr (FRONT) {
       // ---- round trip 2, issue: the robots' target-cell grid tiles first
       // (the moves wait only for them), then every staged tile; block
@@ -2355,9 +2437,16 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
         // robot's post-move cell: a dependent round trip, landed before the
         // merge (vis_items_land).  No row plane is scattered: nothing marches
         stage_load(s, C, g0, true, I, &F);
+        if constexpr (CT::CARRY) {
+          // (the launch's last step reads its own row again: fuse_prefetch_step)
+          const uint8_t* an = io.actions + (int64_t)(fuse_prefetch_step(k, io.num_steps) - k) * io.stride.actions;
+          act_next = el<O32>(an, eN + ag);
+          act0_next = el<O32>(an, eN);
+        }
         uint32_t xy_after[NSM];
         moves_front(s, C, F, !inb || ((tt >> tile_bit(tx, ty)) & 1ull), (uint32_t)tx | ((uint32_t)ty << 16), act,
                     moved0, -s.pen, xy_after);
+        if constexpr (CT::CARRY) xy_next = pick_u<NSM>(xy_after, ag);
         int xk[KI], yk[KI];
 #pragma unroll
         for (int k = 0; k < KI; ++k) {
@@ -2396,7 +2485,10 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
     }
     // count_nonzero(grid > 0) for percent_covered: kept in a register until
     // the reward (no wait here)
-    const int numfree = el<O32>(s.numfree, g0);
+    // (CARRY: carried with env_grid)
+    int numfree;
+    if (CT::CARRY && LOOP && carried) numfree = (int)Hd.numfree;
+    else numfree = el<O32>(s.numfree, g0);
     __syncthreads();
     STAMP(2);
     reload_state<SH, EPW, LOOP>(s, io, k);
@@ -2429,7 +2521,7 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
     uint32_t free_old_r = free_old, vis_old_r = vis_old;
     int currstep_r = currstep0;
     double dthresh_r = dthresh0;
-    if constexpr (EPW == 1) {
+    if constexpr (EPW == 1 && !CT::CARRY) {  // (CARRY: they are VGPRs of the head)
       const RecLo rl = rec_lo(el<O32>(s.rec, e));
       free_old_r = rl.free_cnt;
       vis_old_r = rl.vis_cnt;
@@ -2504,6 +2596,24 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
         }
         rec_store_counts(el<O32>(s.rec, e), dt, fc, vc, cs);
         c->do_reset = do_reset ? 1 : 0;
+      }
+      if constexpr (CT::CARRY) {
+        // the head of the next step: what this step stores, and will store
+        // below, kept in registers as well.  (A reset leaves `ok` clear: the
+        // next step loads what reset_env wrote.)
+        const uint64_t mv = c->moved;
+        Hd.xy = xy_next;
+        Hd.act = act_next;
+        Hd.act0 = act0_next;
+        Hd.numfree = (uint32_t)numfree;
+        Hd.moved_lo = (uint32_t)mv;
+        Hd.moved_hi = (uint32_t)(mv >> 32);
+        Hd.free_cnt = fc;
+        Hd.vis_cnt = vc;
+        Hd.currstep = (uint32_t)cs;
+        Hd.dt_lo = (uint32_t)__double2loint(dt);
+        Hd.dt_hi = (uint32_t)__double2hiint(dt);
+        Hd.ok = do_reset ? 0u : 1u;
       }
     }
     // dist_reward: the POST terms of the maps whose M is still known (the
@@ -2655,10 +2765,12 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
 // this launch's stores -- pos, rec, the free / obstacle tiles (plain stores),
 // the union tiles (global_atomic_or, executed at L2), reset_env's cleared maps
 // -- was stored by this workgroup, so a workgroup-scope release / acquire
-// orders it (the release waits for the stores and atomics to be acknowledged;
-// the CU's L1 is write-through and shared by the workgroup's waves, and an
-// atomic leaves no stale copy of its line there -- tools/micro/loop_probe.hip
-// checks exactly that).  Several waves also meet at a barrier between the two
+// orders it (the CU's L1 is write-through and shared by the workgroup's waves,
+// and an atomic leaves no stale copy of its line there -- tools/micro/
+// loop_probe.hip checks exactly that; in the one-wave kernels the pair emits
+// no instruction, and what waits for the previous step's stores is the
+// s_waitcnt vmcnt(0) of the next step's first loads: one in-order counter
+// for loads and stores).  Several waves also meet at a barrier between the two
 // fences: a fast wave must not re-initialise LDS that a slow wave still reads
 // (the obs), and must not load state a slow wave has not stored yet.
 template <int NT, int EPW, typename WT, class SH>
@@ -2682,6 +2794,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
     return valid;
   };
   [[maybe_unused]] LaneK K = {};  // LANEK: step 0's lane constants, carried through the loop
+  HeadK Hd = {};                  // CARRY: the env head, from step 0 on
   // ---- step 0 (mc_step, mc_reset: the only one), straight-line: the kernel
   // arguments as the compiler likes to load them, all at the entry
   {
@@ -2691,7 +2804,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
     CT C;
     const bool valid = place(s, threadIdx.x, C);
     if constexpr (CT::LANEK) K.ob = C.ob.pack();
-    env_step(s, io, C, valid, 0);
+    env_step(s, io, C, valid, 0, Hd);
   }
   // ---- steps 1 .. num_steps - 1 of a fused launch: a second copy of the step
   // in a loop.  (One copy, looped from step 0, made every launch slower: the
@@ -2727,7 +2840,12 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
       asm volatile("" : "+v"(K.ob));
       C.ob = ObsRoles::unpack(K.ob);
     }
-    env_step<CT, CT::LANEK>(s, io, C, valid, k);
+    if constexpr (CT::CARRY) {
+      asm volatile("" : "+v"(Hd.xy), "+v"(Hd.act), "+v"(Hd.act0), "+v"(Hd.grid), "+v"(Hd.numfree));
+      asm volatile("" : "+v"(Hd.moved_lo), "+v"(Hd.moved_hi), "+v"(Hd.free_cnt), "+v"(Hd.vis_cnt));
+      asm volatile("" : "+v"(Hd.currstep), "+v"(Hd.dt_lo), "+v"(Hd.dt_hi), "+v"(Hd.ok));
+    }
+    env_step<CT, CT::LANEK>(s, io, C, valid, k, Hd);
   }
 }
 

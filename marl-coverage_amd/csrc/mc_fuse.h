@@ -51,4 +51,12 @@ inline bool fuse_chunk(int64_t K, int S, int64_t i, const int64_t (&stride)[FUSE
   return true;
 }
 
+// The step whose action row step k of a launch of num_steps steps (0 <= k <
+// num_steps) prefetches while it runs (the env kernel's carried head,
+// mc_env_step.h): the next one, and at the launch's last step its own row
+// again -- the caller's buffer may end with the launch's last row, so no
+// address past it is formed.  The kernel adds (this - k) * stride to step k's
+// row.  (constexpr: host and device alike)
+constexpr int fuse_prefetch_step(int k, int num_steps) { return (int64_t)k + 1 < num_steps ? k + 1 : k; }
+
 }  // namespace mc
