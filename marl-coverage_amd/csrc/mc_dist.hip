@@ -81,7 +81,8 @@ constexpr int kCh = kDtThreads / kPairs;       // row chunks per column pair: th
 constexpr int kSP = kCh == 64 ? 34 : 36;
 constexpr int kInf = 1 << 20;                  // "no covered cell in this row"
 constexpr int kMaxRows = 832;                  // RX limit of the largest instantiation
-constexpr int kRowOff = 1024;                  // g - u + kRowOff > 0 (u < kMaxRows)
+constexpr int kRowOff = 1024;                  // column_pass's row offset here: g - u + kRowOff > 0 (u < kMaxRows)
+static_assert(kRowOff >= kMaxRows, "g - u + kRowOff > 0 for every row dist_kernel_t accepts");
 constexpr int kMaxTrack = kDistStrips;         // strips whose max(d) the cache pass can skip by
 #ifndef MC_FAST_TILES  // build knob (A/B): tiles the cache fast path stages (box + 25 around the robot)
 // (1024 since round 5: 8 KB of LDS, more workgroups per CU; a box past it
@@ -92,7 +93,6 @@ constexpr int kMaxTrack = kDistStrips;         // strips whose max(d) the cache 
 constexpr int kFastTiles = MC_FAST_TILES;
 typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
 constexpr u16x2 kNone2 = {0xFFFF, 0xFFFF};
-constexpr u16x2 kRowOff2 = {kRowOff, kRowOff};
 __device__ __forceinline__ u16x2 splat2(int v) { return u16x2{(uint16_t)v, (uint16_t)v}; }
 
 // The thread index as an opaque value: the compiler can neither hoist what
@@ -332,9 +332,24 @@ __device__ __forceinline__ void row_pass_none(uint2* grow) {
 // u0, made opaque per strip: the compiler would otherwise hoist CL
 // loop-invariant row values out of the strip loop (and spill them).  One
 // workgroup barrier between the G reads and the scans.
-template <int CL, int CH, int SP>
+//
+// ROFF keeps the "up" scan's g + ROFF - u from clamping at 0: every row of
+// the strip is u < CL * CH <= ROFF (past row ROFF + g it clamped, and every
+// cell below got up = u' - ROFF: dist_big_kernel with the other kernel's 1024).
+// The u16 headroom, for ROFF <= 2048 and u <= 1087 (the longest strip): a row
+// with a covered cell has g <= RY - 1 <= 32766 (mc_create rejects more than
+// 32767 extended columns), so g + ROFF <= 34814 and g + u <= 33853 do not
+// saturate, and a real d is at most RX + RY - 2 <= 33853.  A row without one
+// holds g >= 0xFFFF - kStrip (row_pass_none, the row passes' A and Bd): g +
+// ROFF saturates, tp >= 0xFFFF - 1087 = 64448 is above every real tp, an "up"
+// out of it is >= 0xFFFF - ROFF >= 63487 and a "down" >= 0xFFFF - kStrip -
+// 1087 = 64416, both above every real d: min(up, down) is a real distance
+// whenever the map has a covered cell (a map without one is not transformed).
+template <int CL, int CH, int SP, int ROFF>
 __device__ __forceinline__ int column_pass(const uint16_t* G, int u0c, int pair, uint32_t rowmask, u16x2 (&tp)[CL],
                                            uint32_t& klo, uint32_t& khi) {
+  static_assert(ROFF >= CL * CH && ROFF <= 2048, "the row offset covers the strip's rows and keeps the u16 headroom");
+  constexpr u16x2 kRowOff2 = {ROFF, ROFF};
   int u0 = u0c;
   asm volatile("" : "+v"(u0));
   const uint32_t* g32 = reinterpret_cast<const uint32_t*>(G) + u0 * (SP / 2) + pair;
@@ -1244,7 +1259,7 @@ __global__ __launch_bounds__(kDtThreads, 4) void dist_kernel_t(DistArgs args) {
       // ---- column pass: this thread's column pair and chunk of kCL rows
       u16x2 tp[kCL];  // d of the chunk's cells
       uint32_t klo, khi;
-      const int u0 = column_pass<kCL, kCh, kSP>(G, u0c, pair, rowmask, tp, klo, khi);
+      const int u0 = column_pass<kCL, kCh, kSP, kRowOff>(G, u0c, pair, rowmask, tp, klo, khi);
       const int v = c0 + 2 * pair;
       const int collect = thr >= 0 ? thr : cthr;
       // cells with d >= collect into the LDS list; an overflowed list (count
@@ -1715,6 +1730,8 @@ constexpr int kBigCh = 64;                    // row chunks per column pair: one
 constexpr int kBigCL = 17;                    // rows per chunk
 constexpr int kBigSP = 34;                    // strip row stride (u16; 17 dwords: distinct banks)
 constexpr int kBigMaxRows = kBigCh * kBigCL;  // 1,088 extended rows
+constexpr int kBigRowOff = 2048;              // column_pass's row offset: rows past kRowOff = 1024 (headroom: there)
+static_assert(kBigRowOff >= kBigMaxRows, "g - u + kBigRowOff > 0 for every row dist_big_kernel accepts");
 
 struct BigLds {
   size_t nxt, wc, strip, tgt, total;
@@ -1893,7 +1910,7 @@ __global__ __launch_bounds__(kBigThreads, 1) void dist_big_kernel(State s, int p
       // ---- column pass: 64 chunks of a column pair per wave
       u16x2 tp[kBigCL];
       uint32_t klo, khi;
-      const int u0 = column_pass<kBigCL, kBigCh, kBigSP>(G, u0c, pair, rowmask, tp, klo, khi);
+      const int u0 = column_pass<kBigCL, kBigCh, kBigSP, kBigRowOff>(G, u0c, pair, rowmask, tp, klo, khi);
       const int v = c0 + 2 * pair;
       best_update(klo, khi, v, RY, bestkey, bestv);
       const bool keep = v + 1 >= tv_lo && v <= tv_hi && u0 + kBigCL > tu_lo && u0 <= tu_hi;

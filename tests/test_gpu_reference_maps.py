@@ -9,8 +9,10 @@ tests/golden/maps; SURVEY 8(f) rank 4, gridmaker.py:82-102).
   batch against the oracle, at the C2 and C4 sensor configs.
 * dist_reward on that map (1,079 extended rows: the big-map distance
   kernel, mc_dist.hip dist_big_kernel) against the oracle, (M, witness) of
-  every map checked against a fresh transform; a grid past the big kernel's
-  1,088 rows is rejected by mc_create with a message.
+  every map checked against a fresh transform, from random starts and with
+  the robots injected in the map's last rows (extended rows past 1,024); a
+  grid past the big kernel's 1,088 rows is rejected by mc_create with a
+  message.
 """
 import os
 
@@ -94,6 +96,29 @@ def test_bg2_1073_dist_reward_matches_oracle(torch_cuda):
     resets = run_against_oracle(torch, env, cfg, np.random.RandomState(79), 16, [0, 1], 5, "bg2_1073 dist",
                                 dist_check=True, sentinel_p=0.0)
     assert resets >= 2
+
+
+def test_bg2_1073_dist_reward_last_rows(torch_cuda):
+    """The same config with the eight robots of two envs injected at the map's
+    eight bottom-most cells with grid > 0 (ties: the smallest column), all in
+    extended rows past 1030: the big-map kernel's column pass below row 1024,
+    where coverage is (the random starts of the test above hardly ever put any
+    there).  6 steps against the oracle, no auto-reset (maxsteps 1000), every
+    (M, witness) against a fresh transform.  test_gpu_dist_field.py compares
+    the whole field at 1,088 rows."""
+    import marlcov
+    torch = torch_cuda
+    cfg = base_cfg(numrobot=4, dist_reward=1, maxsteps=1000)
+    g = big_map()
+    cells = np.argwhere(g > 0)
+    cells = cells[np.lexsort((cells[:, 1], -cells[:, 0]))][:8] + 1  # padded coordinates
+    env = marlcov.BatchCoverageEnv(cfg, 2, grids=[g], auto_reset=True, seed=5)
+    assert env.width + 2 * env.pad == 1079
+    assert (cells[:, 0] + env.pad > 1030).all(), cells
+    env.reset(positions=cells.reshape(2, 4, 2).astype(np.int32))
+    resets = run_against_oracle(torch, env, cfg, np.random.RandomState(1030), 6, [0, 1], 5, "bg2_1073 last rows",
+                                dist_check=True, sentinel_p=0.0)
+    assert resets == 0
 
 
 def test_dist_reward_rows_past_the_big_kernel_are_rejected(torch_cuda):
