@@ -886,15 +886,12 @@ __device__ __forceinline__ VisTiles<CT::KI> vis_items_load(const State& s, const
                                                            const int (&x)[CT::KI], const int (&y)[CT::KI]) {
   constexpr int KI = CT::KI, LPE = CT::LPE, H = CT::SH::H;
   const int items = s.N * s.TW * s.TW;
-  const uint32_t last = (uint32_t)s.G * (uint32_t)s.Wp * (uint32_t)s.Lp - 1u;  // never past the table
   VisTiles<KI> V;
 #pragma unroll
   for (int k = 0; k < KI; ++k) {
-    const uint32_t ri = (uint32_t)(I.gi[k] - ((x[k] - H) >> 3)), rj = (uint32_t)(I.gj[k] - ((y[k] - H) >> 3));
-    V.on[k] = (C.sub + k * LPE < items) & (ri < 4u) & (rj < 4u);
-    const uint32_t rec = min(vis_index(s.Wp, s.Lp, g, x[k], y[k]), last);
-    const char* p = reinterpret_cast<const char*>(s.vis_tab) + (size_t)rec * (kVisRecWords * 4) +
-                    (V.on[k] ? (ri * 4u + rj) * 8u : 0u);
+    const char* p = reinterpret_cast<const char*>(s.vis_tab) +
+                    vis_item_offset(s.G, s.Wp, s.Lp, H, g, I.gi[k], I.gj[k], x[k], y[k], C.sub + k * LPE < items,
+                                    &V.on[k]);
     V.m[k] = *reinterpret_cast<const uint64_t*>(p);
     V.mo[k] = kVisSplit ? *reinterpret_cast<const uint64_t*>(p + kVisTiles * 8) : 0ull;
   }
@@ -927,6 +924,58 @@ __device__ __forceinline__ void vis_items_land(const State& s, const CT& C, Item
       C.L.fp[idx] = I.mf[k];
     }
   }
+}
+
+// The record tiles the fused loop loads a step ahead (EnvCfg::CARRY, unsplit
+// records).  Step k knows every robot's cell after its moves and step k + 1's
+// action bytes (HeadK), and the grid and the table are read-only: it predicts
+// each robot's cell after step k + 1 (fuse_predict_cell, mc_fuse.h: its own
+// target's grid bit, other robots not looked at) and issues, per item, the load
+// vis_items_load would issue in step k + 1 for that cell.  Step k + 1's loop
+// copy takes them in place of its dependent round trip when the wave carries
+// its head (so step k ran in this launch and filled these words) and the moves
+// gave every item's robot the predicted cell -- one wave-uniform test;
+// otherwise the whole wave loads as without the prefetch, so a wrong
+// prediction costs time only.  Nothing here is ever stored: memory stays
+// authoritative exactly as HeadK describes.  The tiles are in flight across
+// the loop's back edge and pass through no asm there (a use would wait).
+template <int KI>
+struct VisK {
+  uint64_t m[KI];     // the items' tiles of the predicted cells' records
+  uint32_t cell[KI];  // item k's robot's predicted cell after the next step, x | y << 16
+  uint32_t fl;        // bit k: item k has a tile of the record (VisTiles::on); bit 8: the lane's robot's next target is blocked
+};
+
+// issue, in step k after the tile stores.  xy_after: the robots' cells after step
+// k's moves (the next step's block origins, as front_regs derives them);
+// cell_own: the predicted cell of the lane's robot; I: this step's items (the
+// item-to-agent assignment of a lane never changes)
+template <class CT, int NS>
+__device__ __forceinline__ void vis_prefetch(const State& s, const CT& C, int g, const Items<CT::KI>& I,
+                                             const uint32_t (&xy_after)[NS], uint32_t cell_own, bool blk,
+                                             VisK<CT::KI>& P) {
+  constexpr int KI = CT::KI, LPE = CT::LPE, H = CT::SH::H;
+  const int items = s.N * s.TW * s.TW;
+  uint32_t pc[NS];
+#pragma unroll
+  for (int i = 0; i < NS; ++i) {
+    if constexpr (FrontQuad<NS>::ok) pc[i] = (uint32_t)quad_bcast<NS>((int)cell_own, i);
+    else pc[i] = (uint32_t)slot_lane(C, (int)cell_own, i);
+  }
+  uint32_t fl = blk ? 0x100u : 0u;
+#pragma unroll
+  for (int k = 0; k < KI; ++k) {
+    const uint32_t xa = pick_u<NS>(xy_after, I.a[k]), cell = pick_u<NS>(pc, I.a[k]);
+    const int bx = ((int)(xa & 0xFFFFu) - s.H - 1) >> 3, by = ((int)(xa >> 16) - s.H - 1) >> 3;
+    bool on;
+    const char* p = reinterpret_cast<const char*>(s.vis_tab) +
+                    vis_item_offset(s.G, s.Wp, s.Lp, H, g, bx + I.ti[k], by + I.tj[k], (int)(cell & 0xFFFFu),
+                                    (int)(cell >> 16), C.sub + k * LPE < items, &on);
+    P.m[k] = *reinterpret_cast<const uint64_t*>(p);
+    P.cell[k] = cell;
+    fl |= on ? 1u << k : 0u;
+  }
+  P.fl = fl;
 }
 
 // --------------------------------------------------------------------------
@@ -2245,10 +2294,12 @@ constexpr int env_min_waves() {
 // env (a short last workgroup's idle slot writes nothing, in any step).
 // Hd (CT::CARRY): the carried env head -- every step refills it, and the loop
 // copy builds round trip 1's results from it when no slot of the wave is stale
-// (HeadK has the rule).
+// (HeadK has the rule).  VK (CT::CARRY): the record tiles prefetched for the
+// next step (VisK).
 template <class CT, bool LOOP = false>
 __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool valid, const int k,
-                                         [[maybe_unused]] HeadK& Hd) {
+                                         [[maybe_unused]] HeadK& Hd,
+                                         [[maybe_unused]] VisK<CT::KI>& VK) {
   using WT = typename CT::WT;
   using SH = typename CT::SH;
   constexpr int NT = CT::NT, EPW = CT::EPW;
@@ -2421,6 +2472,13 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
     [[maybe_unused]] VisTiles<KI> V;  // VISTAB: the items' tiles of their robots' records, in flight
     // CARRY: the next step's action bytes, in flight during this step, and the lane's robot's cell after the moves
     [[maybe_unused]] uint32_t act_next = 0, act0_next = 0, xy_next = 0;
+    // ... and whether this step prefetches the next one's record tiles (VisK;
+    // not at the launch's last step, whose re-read action row is its own),
+    // and whether it may hold the last step's: the loop copy with a carried head
+    constexpr bool kVisPre = CT::CARRY && !kVisSplit;
+    [[maybe_unused]] const bool vis_more = kVisPre && k + 1 < io.num_steps;
+    [[maybe_unused]] const bool vis_held = kVisPre && LOOP && carried;
+    [[maybe_unused]] uint32_t xy_after[NSM > 0 ? NSM : 1];
     if constexpr (FRONT) {
       // ---- round trip 2, issue: the robots' target-cell grid tiles first
       // (the moves wait only for them), then every staged tile; block
@@ -2430,8 +2488,22 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
       const int dx = (act == 0) - (act == 2), dy = (act == 1) - (act == 3);
       const int tx = p0.x + dx, ty = p0.y + dy;
       const bool inb = (unsigned)tx < (unsigned)s.Wp && (unsigned)ty < (unsigned)s.Lp;
-      const uint64_t tt = ld_tile<O32>(s.grid_neg, __umul24((uint32_t)g0, (uint32_t)s.MT) +
-                                                       tile_index24(s.TCS, inb ? tx >> 3 : 0, inb ? ty >> 3 : 0));
+      uint64_t tt = 0;
+      [[maybe_unused]] bool blk_held = false;
+      if constexpr (kVisPre && LOOP) {
+        // the target's bit as the last step read it (VisK::fl); a wave that
+        // does not carry reads it now and waits here, inside its arm
+        if (vis_held) {
+          blk_held = (VK.fl & 0x100u) != 0;
+        } else {
+          tt = ld_tile<O32>(s.grid_neg, __umul24((uint32_t)g0, (uint32_t)s.MT) +
+                                            tile_index24(s.TCS, inb ? tx >> 3 : 0, inb ? ty >> 3 : 0));
+          blk_held = !inb || ((tt >> tile_bit(tx, ty)) & 1ull);
+        }
+      } else {
+        tt = ld_tile<O32>(s.grid_neg, __umul24((uint32_t)g0, (uint32_t)s.MT) +
+                                          tile_index24(s.TCS, inb ? tx >> 3 : 0, inb ? ty >> 3 : 0));
+      }
       if constexpr (CT::VISTAB) {
         // ... and after the moves every item's tile of the record of its
         // robot's post-move cell: a dependent round trip, landed before the
@@ -2443,9 +2515,8 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
           act_next = el<O32>(an, eN + ag);
           act0_next = el<O32>(an, eN);
         }
-        uint32_t xy_after[NSM];
-        moves_front(s, C, F, !inb || ((tt >> tile_bit(tx, ty)) & 1ull), (uint32_t)tx | ((uint32_t)ty << 16), act,
-                    moved0, -s.pen, xy_after);
+        const bool tgt_blk = (kVisPre && LOOP) ? blk_held : (!inb || ((tt >> tile_bit(tx, ty)) & 1ull));
+        moves_front(s, C, F, tgt_blk, (uint32_t)tx | ((uint32_t)ty << 16), act, moved0, -s.pen, xy_after);
         if constexpr (CT::CARRY) xy_next = pick_u<NSM>(xy_after, ag);
         int xk[KI], yk[KI];
 #pragma unroll
@@ -2454,7 +2525,31 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
           xk[k] = (int)(xy & 0xFFFFu);
           yk[k] = (int)(xy >> 16);
         }
-        V = vis_items_load(s, C, g0, I, xk, yk);
+        // (VisK) the prefetched tiles where the moves gave every item's robot
+        // of the wave's active slots its predicted cell
+        bool vis_hit = false;
+        if constexpr (kVisPre && LOOP) {
+          if (vis_held) {
+            bool miss = false;
+#pragma unroll
+            for (int k = 0; k < KI; ++k) miss |= ((uint32_t)xk[k] | ((uint32_t)yk[k] << 16)) != VK.cell[k];
+            vis_hit = __ballot(miss) == 0;
+          }
+        }
+        if ((kVisPre && LOOP) && vis_hit) {
+#pragma unroll
+          for (int k = 0; k < KI; ++k) {
+            V.m[k] = VK.m[k];
+            V.mo[k] = 0ull;
+            V.on[k] = ((VK.fl >> k) & 1u) != 0;
+          }
+        } else {
+          V = vis_items_load(s, C, g0, I, xk, yk);
+          // the reloading arm's loads land inside it (a real s_waitcnt, as in
+          // the head's loading arm): joined with one wait after the branch,
+          // the predicted path would wait for its mask tiles there too
+          if constexpr (kVisPre && LOOP) __builtin_amdgcn_s_waitcnt(0x0F70);
+        }
       } else {
         stage_load(s, C, g0, true, I, &F);
         moves_front(s, C, F, !inb || ((tt >> tile_bit(tx, ty)) & 1ull), (uint32_t)tx | ((uint32_t)ty << 16), act,
@@ -2537,6 +2632,23 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
       dprek = pr[1 + k];
     }
     if constexpr (CT::VISTAB) vis_items_land(s, C, I, V);
+    // (VisK) the lane's robot's target cell in the next step, from its cell
+    // after this step's moves and the next action byte (landed with the record
+    // tiles: loads return in order); its grid tile lands during the merge and
+    // the reward, and is used after the tile stores (vis_prefetch)
+    [[maybe_unused]] int ntx = 0, nty = 0;
+    [[maybe_unused]] bool ninb = false;
+    [[maybe_unused]] uint64_t tn = 0;
+    if constexpr (kVisPre) {
+      if (vis_more) {
+        const int an = (int)act_next;
+        ntx = (int)(xy_next & 0xFFFFu) + ((an == 0) - (an == 2));
+        nty = (int)(xy_next >> 16) + ((an == 1) - (an == 3));
+        ninb = (unsigned)ntx < (unsigned)s.Wp && (unsigned)nty < (unsigned)s.Lp;
+        tn = ld_tile<O32>(s.grid_neg, __umul24((uint32_t)g0, (uint32_t)s.MT) +
+                                          tile_index24(s.TCS, ninb ? ntx >> 3 : 0, ninb ? nty >> 3 : 0));
+      }
+    }
     sense_and_merge<CT, CT::VISTAB>(s, C, I);
     __syncthreads();
     STAMP(5);
@@ -2651,6 +2763,16 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
     reload_state<SH, EPW, LOOP>(s, io, k);
     if (!do_reset) {
       store_tiles(s, C, I);
+      // (VisK) the next step's record tiles, issued here and not right after
+      // the merge: the target's grid tile has landed by now without a wait
+      // (right after the merge the step waited for it, and lost what the
+      // prefetch gains), and a reset issues nothing
+      if constexpr (kVisPre) {
+        if (vis_more) {
+          const bool nblk = !ninb || ((tn >> tile_bit(ntx, nty)) & 1ull);
+          vis_prefetch(s, C, g0, I, xy_after, fuse_predict_cell(xy_next, act_next, nblk), nblk, VK);
+        }
+      }
       STAMP(7);
     } else {
       reset_env(s, C, nullptr);  // the finished episode's tiles are not stored
@@ -2675,6 +2797,11 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
     // needs the full transform
     dlist = s.dist && C.sub < N && L.dm[C.sub] < 0;
     if (C.sub == 0 && sentinel) sentinel_done(s, io, e, g0, free_old, currstep0);
+    // (CARRY: the grid tiles stage_load read for nothing land here, inside the
+    // arm.  It is laid out ahead of the active path, and a load it left in
+    // flight made that path's moves wait for all but its newest loads, the
+    // last step's stores among them)
+    if constexpr (CT::CARRY) __builtin_amdgcn_s_waitcnt(0x0F70);
   }
   __syncthreads();
 
@@ -2795,6 +2922,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
   };
   [[maybe_unused]] LaneK K = {};  // LANEK: step 0's lane constants, carried through the loop
   HeadK Hd = {};                  // CARRY: the env head, from step 0 on
+  VisK<CT::KI> VK = {};           // CARRY: the next step's record tiles, from step 0 on
   // ---- step 0 (mc_step, mc_reset: the only one), straight-line: the kernel
   // arguments as the compiler likes to load them, all at the entry
   {
@@ -2804,7 +2932,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
     CT C;
     const bool valid = place(s, threadIdx.x, C);
     if constexpr (CT::LANEK) K.ob = C.ob.pack();
-    env_step(s, io, C, valid, 0, Hd);
+    env_step(s, io, C, valid, 0, Hd, VK);
   }
   // ---- steps 1 .. num_steps - 1 of a fused launch: a second copy of the step
   // in a loop.  (One copy, looped from step 0, made every launch slower: the
@@ -2845,7 +2973,7 @@ __global__ __launch_bounds__(NT, (env_min_waves<NT, SH>())) void env_kernel(EnvA
       asm volatile("" : "+v"(Hd.moved_lo), "+v"(Hd.moved_hi), "+v"(Hd.free_cnt), "+v"(Hd.vis_cnt));
       asm volatile("" : "+v"(Hd.currstep), "+v"(Hd.dt_lo), "+v"(Hd.dt_hi), "+v"(Hd.ok));
     }
-    env_step<CT, CT::LANEK>(s, io, C, valid, k, Hd);
+    env_step<CT, CT::LANEK>(s, io, C, valid, k, Hd, VK);
   }
 }
 

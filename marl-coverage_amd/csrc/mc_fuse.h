@@ -59,4 +59,19 @@ inline bool fuse_chunk(int64_t K, int S, int64_t i, const int64_t (&stride)[FUSE
 // row.  (constexpr: host and device alike)
 constexpr int fuse_prefetch_step(int k, int num_steps) { return (int64_t)k + 1 < num_steps ? k + 1 : k; }
 
+// The cell (x | y << 16) the carried head predicts for a robot after the next
+// step, from its cell before it, its action byte and whether the byte's target
+// cell is blocked (out of bounds, or grid < 0): moves_front's rule for one
+// robot alone.  Other robots are not looked at: a robot held back by one, or
+// let through by one that left, is a misprediction, which the step that uses
+// the prefetched visibility record finds by comparing with the cell the moves
+// gave, and then loads the record as a step without the prefetch does.
+constexpr uint32_t fuse_target_cell(uint32_t xy, uint32_t act) {
+  return (uint32_t)((int)(xy & 0xFFFFu) + ((act == 0) - (act == 2))) |
+         ((uint32_t)((int)(xy >> 16) + ((act == 1) - (act == 3))) << 16);
+}
+constexpr uint32_t fuse_predict_cell(uint32_t xy, uint32_t act, bool blocked) {
+  return (act <= 3 && !blocked) ? fuse_target_cell(xy, act) : xy;
+}
+
 }  // namespace mc

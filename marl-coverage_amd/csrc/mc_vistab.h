@@ -40,6 +40,23 @@ __host__ __device__ inline uint32_t vis_index(int Wp, int Lp, int g, int x, int 
   return ((uint32_t)g * (uint32_t)Wp + (uint32_t)x) * (uint32_t)Lp + (uint32_t)y;
 }
 
+// Byte offset, in the table of a pool of G grids of Wp x Lp cells, of map tile
+// (gi, gj)'s tile of the record of cell (x, y) of grid g (H: the lidar's
+// range; the record's origin tile is ((x - H) >> 3, (y - H) >> 3)).  on: the
+// tile is one of the record's 4 x 4 (and the item is `live`); without it the
+// record's first tile is addressed.  Clamped to the table whatever the
+// arguments hold: the step kernel loads through it unpredicated, and a step
+// ahead for a predicted cell (mc_env_step.h vis_items_load, vis_prefetch).
+__host__ __device__ inline size_t vis_item_offset(int G, int Wp, int Lp, int H, int g, int gi, int gj, int x, int y,
+                                                  bool live, bool* on) {
+  const uint32_t last = (uint32_t)G * (uint32_t)Wp * (uint32_t)Lp - 1u;  // never past the table
+  const uint32_t ri = (uint32_t)(gi - ((x - H) >> 3)), rj = (uint32_t)(gj - ((y - H) >> 3));
+  *on = live & (ri < 4u) & (rj < 4u);
+  const uint32_t idx = vis_index(Wp, Lp, g, x, y);
+  const uint32_t rec = idx < last ? idx : last;
+  return (size_t)rec * (kVisRecWords * 4) + (*on ? (ri * 4u + rj) * 8u : 0u);
+}
+
 // isInBounds + grid < 0 of one grid's tiles (neg: its MT tiles in tile_index order)
 __host__ __device__ inline bool vis_blocked(const uint64_t* neg, int TCS, int Wp, int Lp, int x, int y) {
   if (x < 0 || y < 0 || x >= Wp || y >= Lp) return true;
