@@ -15,8 +15,15 @@ namespace mc {
 // shareMaps (dec_grid_rl.py:423-447), run before the step kernel when
 // map_sharing is on: agent i's maps <- OR over {j: adj(i,j) or i==j}, with
 // adj from the positions at the start of the step (the last comm graph).
-// grid = (ceil(TR*TC / 64), B); block = 64 lanes, one tile position each.
+// grid = (ceil(TR*TC / 64), B); block = 64 lanes (one wave), one tile
+// position each.  Dynamic LDS: the old words of one map kind, [N][64], and
+// the graph as one 64-bit row mask per agent, [64] -- N * 512 + 512 B, 33,280
+// B at the 64 robots mc_create accepts.  The free maps go through the staging
+// rows first, the obstacle maps after them: a lane reads back only its own
+// column, so the two kinds never need to be resident together.
 // --------------------------------------------------------------------------
+constexpr size_t share_lds(int N) { return (size_t)N * 64 * 8 + 64 * 8; }
+
 __global__ __launch_bounds__(64) void share_kernel(State s, const uint8_t* __restrict__ actions) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int e = blockIdx.y;
@@ -25,37 +32,34 @@ __global__ __launch_bounds__(64) void share_kernel(State s, const uint8_t* __res
   const size_t mw = (size_t)s.MT;
   const int lane = threadIdx.x;
   const size_t w = (size_t)blockIdx.x * 64 + lane;
-  uint64_t* fo = reinterpret_cast<uint64_t*>(smem);   // [N][64]
-  uint64_t* oo = fo + (size_t)N * 64;                  // [N][64]
-  int32_t* px = reinterpret_cast<int32_t*>(oo + (size_t)N * 64);
-  int32_t* py = px + 64;
-  if (lane < N) {
-    px[lane] = s.pos[((size_t)e * N + lane) * 2];
-    py[lane] = s.pos[((size_t)e * N + lane) * 2 + 1];
-  }
-  uint64_t* f = s.freem + (size_t)e * N * mw + w;
-  uint64_t* o = s.obstm + (size_t)e * N * mw + w;
-  const bool live = w < mw;
+  uint64_t* old = reinterpret_cast<uint64_t*>(smem);  // [N][64]
+  uint64_t* adj = old + (size_t)N * 64;               // [64]: bit j of adj[i] = j's maps reach i
+  // lane i builds row i of the graph (N <= 64: one lane per agent)
+  const int32_t* pos = s.pos + (size_t)e * N * 2;
+  const int xi = lane < N ? pos[lane * 2] : 0, yi = lane < N ? pos[lane * 2 + 1] : 0;
+  uint64_t row = 0;
   for (int j = 0; j < N; ++j) {
-    fo[j * 64 + lane] = live ? f[j * mw] : 0ull;
-    oo[j * 64 + lane] = live ? o[j * mw] : 0ull;
+    const int d = max(abs(xi - pos[j * 2]), abs(yi - pos[j * 2 + 1]));
+    if (d <= s.comm_r || lane == j) row |= 1ull << j;
   }
-  __syncthreads();
-  if (!live) return;
+  adj[lane] = lane < N ? row : 0ull;
+  const bool live = w < mw;
   uint32_t cnt = 0;
-  for (int i = 0; i < N; ++i) {
-    uint64_t fn = 0, on = 0;
-    for (int j = 0; j < N; ++j) {
-      const int d = max(abs(px[i] - px[j]), abs(py[i] - py[j]));
-      if (d <= s.comm_r || i == j) {
-        fn |= fo[j * 64 + lane];
-        on |= oo[j * 64 + lane];
+  for (int kind = 0; kind < 2; ++kind) {
+    uint64_t* m = (kind == 0 ? s.freem : s.obstm) + (size_t)e * N * mw + w;
+    for (int j = 0; j < N; ++j) old[j * 64 + lane] = live ? m[j * mw] : 0ull;
+    __syncthreads();  // adj rows (first pass); the staging column is the lane's own
+    if (live) {
+      for (int i = 0; i < N; ++i) {
+        const uint64_t r = adj[i];
+        uint64_t v = 0;
+        for (int j = 0; j < N; ++j)
+          if ((r >> j) & 1) v |= old[j * 64 + lane];
+        const uint64_t vi = old[i * 64 + lane];
+        if (kind == 0) cnt += __popcll(v & ~vi);
+        if (v != vi) m[i * mw] = v;
       }
     }
-    const uint64_t fi = fo[i * 64 + lane], oi = oo[i * 64 + lane];
-    cnt += __popcll(fn & ~fi);
-    if (fn != fi) f[i * mw] = fn;
-    if (on != oi) o[i * mw] = on;
   }
   if (cnt) atomicAdd(&s.rec[e].free_cnt, cnt);
 }
@@ -169,7 +173,8 @@ hipError_t launch_rec_field(const State& s, int off, int width, void* buf, bool 
 hipError_t launch_share(const State& s, const uint8_t* actions, hipStream_t stream) {
   const size_t mw = (size_t)s.MT;
   dim3 grid((unsigned)((mw + 63) / 64), s.B), block(64);
-  const size_t lds = (size_t)s.N * 64 * 16 + 64 * 8;
+  static_assert(share_lds(64) <= 65536, "share_kernel's LDS at the maximum N needs no attribute");
+  const size_t lds = share_lds(s.N);
   hipLaunchKernelGGL(share_kernel, grid, block, lds, stream, s, actions);
   return hipGetLastError();
 }
