@@ -47,6 +47,28 @@ struct ObsFast {
   static constexpr bool ok = EGO > 0 && NS > 0 && EE <= 28 && (NB * EE) % 4 == 0 && (LC == 3 || LC == 4);
 };
 
+// Which (agent, tile) items a lane stages, where the shape fixes it: item k of
+// lane `sub` of an env slot of LPE lanes is number idx = sub + k * LPE of the
+// N * TW * TW items, agent idx / TW^2, tile (ti, tj) = (idx % TW^2 / TW,
+// idx % TW).  With TW^2 a power of two that divides LPE these are bit fields
+// of the lane id and constants of k (stage_load's general form divides twice
+// per item and step), and item k is live in every lane or in none.
+template <int LPE, int N, int TW>
+struct ItemGeo {
+  static constexpr int TW2 = TW * TW;
+  static constexpr int AG = TW2 > 0 ? LPE / TW2 : 0;  // agents one item round of the slot covers
+  static constexpr bool ok = N > 0 && TW > 0 && (TW & (TW - 1)) == 0 && LPE % TW2 == 0 && (AG & (AG - 1)) == 0 &&
+                             (N * TW2) % LPE == 0;
+  __host__ __device__ static constexpr bool live(int k) { return k * LPE < N * TW2; }
+  // the agents item k can belong to: first(k) .. first(k) + AG - 1
+  __host__ __device__ static constexpr int first(int k) { return k * AG; }
+  __host__ __device__ static constexpr int agent(int sub, int k) {  // (a dead item: agent 0, as stage_load has it)
+    return live(k) ? first(k) + (int)(((uint32_t)sub / (uint32_t)TW2) & (uint32_t)(AG - 1)) : 0;
+  }
+  __host__ __device__ static constexpr int ti(int sub) { return (int)(((uint32_t)sub / (uint32_t)TW) & (uint32_t)(TW - 1)); }
+  __host__ __device__ static constexpr int tj(int sub) { return (int)((uint32_t)sub & (uint32_t)(TW - 1)); }
+};
+
 // Everything fixed at compile time for one env_kernel<NT, EPW, WT, SH>
 // instantiation (the kernel's Ctx derives from it, mc_env_step.h).  O32,
 // RAYPROG and VISTAB are also what the instantiation asks of a State before
@@ -119,6 +141,11 @@ struct EnvCfg {
   // back what the wave stored a step earlier: the one-wave table kernels only
   // (the march rows have no VGPRs to give: 13 more words cost them a wave)
   static constexpr bool CARRY = LANEK && VISTAB;
+  // ... and take their items' agents and tiles from the lane id (ItemGeo), run
+  // the union dedup over the (item, lower agent) rounds that leaves and clip
+  // the stored obstacle tiles with two masks (edge_clip, mc_internal.h)
+  using GEO = ItemGeo<LPE, SH::N, window_tiles(SH::H)>;
+  static_assert(!CARRY || GEO::ok, "the carried kernels' items are bit fields of the lane id");
 };
 
 // ---- the instantiations: X(NT, EPW, word, shape, public name), one row per

@@ -279,6 +279,14 @@ struct Items {
   bool masks;                       // f / o / u were loaded (else known zero)
 };
 
+// whether item k of this lane is one of the slot's N * TW * TW items (CARRY:
+// a constant of k, ItemGeo)
+template <class CT>
+__device__ __forceinline__ bool item_live(const CT& C, int k, [[maybe_unused]] int items) {
+  if constexpr (CT::CARRY) return CT::GEO::live(k);
+  else return C.sub + k * CT::LPE < items;
+}
+
 template <typename WT>
 __device__ __forceinline__ void lds_or(WT* p, WT v) {
   if constexpr (sizeof(WT) == 4) atomicOr((unsigned int*)p, (unsigned int)v);
@@ -354,6 +362,27 @@ __device__ __forceinline__ int pick(const int (&R)[NS], int a) {
   return v;
 }
 
+// CARRY: R[agent of item k of lane `sub`] -- the agent is one of the AG that
+// ItemGeo leaves for item k, so the chain has AG - 1 selects, not NS - 1
+template <class CT, typename T, int NS>
+__device__ __forceinline__ T geo_pick(const T (&R)[NS], int sub, int k) {
+  using G = typename CT::GEO;
+  if (!G::live(k)) return R[0];
+  const int f = G::first(k);
+  const uint32_t h = ((uint32_t)sub / (uint32_t)G::TW2) & (uint32_t)(G::AG - 1);
+  // (every candidate through an empty asm first: a select between two loads
+  // of R becomes one load at a selected address, that is R in scratch)
+  T v = R[f];
+  asm volatile("" : "+v"(v));
+#pragma unroll
+  for (int i = 1; i < G::AG; ++i) {
+    T r = R[f + i];
+    asm volatile("" : "+v"(r));
+    v = h == (uint32_t)i ? r : v;
+  }
+  return v;
+}
+
 // the value v of lane lane0 + i of this lane's slot, read with wave-uniform
 // lane indices (v_readlane) and selected by slot
 template <class CT>
@@ -413,8 +442,8 @@ __device__ __forceinline__ void stage_load(const State& s, const CT& C, int g, b
   constexpr int LPE = CT::LPE, KI = CT::KI;
   constexpr bool O32 = CT::O32;
   const Lds<WT>& L = C.L;
-  const int TW = s.TW, TW2 = TW * TW;
-  const int items = s.N * TW2;
+  [[maybe_unused]] const int TW = s.TW, TW2 = TW * TW;
+  [[maybe_unused]] const int items = s.N * TW2;
   const uint32_t mt = (uint32_t)s.MT;
   const uint32_t gb = __umul24((uint32_t)g, mt);  // this env's grid in the pool (tiles)
   const bool square = s.sensor == 1;
@@ -428,14 +457,24 @@ __device__ __forceinline__ void stage_load(const State& s, const CT& C, int g, b
   // every item's block origin read first (one LDS round trip for all items)
 #pragma unroll
   for (int k = 0; k < KI; ++k) {
-    const int idx = C.sub + k * LPE;
-    const bool it = idx < items;
-    const int a = it ? udiv(idx, s.mg_TW2) : 0;
-    const int rem = idx - a * TW2;
-    I.ti[k] = udiv(rem, s.mg_TW);
-    I.tj[k] = rem - I.ti[k] * TW;
+    int a;
+    if constexpr (CT::CARRY) {  // bit fields of the lane id
+      a = CT::GEO::agent(C.sub, k);
+      I.ti[k] = CT::GEO::ti(C.sub);
+      I.tj[k] = CT::GEO::tj(C.sub);
+    } else {
+      const int idx = C.sub + k * LPE;
+      const bool it = idx < items;
+      a = it ? udiv(idx, s.mg_TW2) : 0;
+      const int rem = idx - a * TW2;
+      I.ti[k] = udiv(rem, s.mg_TW);
+      I.tj[k] = rem - I.ti[k] * TW;
+    }
     I.a[k] = a;
-    if constexpr (NS > 0) {
+    if constexpr (NS > 0 && CT::CARRY) {
+      bxa[k] = geo_pick<CT>(F->bx, C.sub, k);
+      bya[k] = geo_pick<CT>(F->by, C.sub, k);
+    } else if constexpr (NS > 0) {
       bxa[k] = pick<NS>(F->bx, a);
       bya[k] = pick<NS>(F->by, a);
     } else {
@@ -445,11 +484,10 @@ __device__ __forceinline__ void stage_load(const State& s, const CT& C, int g, b
   }
 #pragma unroll
   for (int k = 0; k < KI; ++k) {
-    const int idx = C.sub + k * LPE;
     const int gi = bxa[k] + I.ti[k], gj = bya[k] + I.tj[k];
     I.gi[k] = gi;
     I.gj[k] = gj;
-    I.in[k] = (idx < items) & ((unsigned)gi < (unsigned)s.TR) & ((unsigned)gj < (unsigned)s.TC);
+    I.in[k] = item_live(C, k, items) & ((unsigned)gi < (unsigned)s.TR) & ((unsigned)gj < (unsigned)s.TC);
     gt[k] = tile_index24(s.TCS, I.in[k] ? gi : 0, I.in[k] ? gj : 0);
     // tiles outside the map read the mask arrays' zero tile (mc_create)
     if constexpr (CT::KEEP_GT) I.gt[k] = gt[k];
@@ -880,18 +918,17 @@ __device__ __forceinline__ uint32_t pick_u(const uint32_t (&v)[NS], int a) {
   return r;
 }
 
-// issue, after stage_load (I.gi / I.gj).  x[k], y[k]: the cell of item k's robot
+// issue, after stage_load (I.gi / I.gj).  xy[k]: the cell of item k's robot, x | y << 16
 template <class CT>
-__device__ __forceinline__ VisTiles<CT::KI> vis_items_load(const State& s, const CT& C, int g, const Items<CT::KI>& I,
-                                                           const int (&x)[CT::KI], const int (&y)[CT::KI]) {
-  constexpr int KI = CT::KI, LPE = CT::LPE, H = CT::SH::H;
-  const int items = s.N * s.TW * s.TW;
+__device__ __forceinline__ VisTiles<CT::KI> vis_items_load(const State& s, const CT& C, int g,
+                                                           const Items<CT::KI>& I, const uint32_t (&xy)[CT::KI]) {
+  constexpr int KI = CT::KI, H = CT::SH::H;
   VisTiles<KI> V;
 #pragma unroll
   for (int k = 0; k < KI; ++k) {
     const char* p = reinterpret_cast<const char*>(s.vis_tab) +
-                    vis_item_offset(s.G, s.Wp, s.Lp, H, g, I.gi[k], I.gj[k], x[k], y[k], C.sub + k * LPE < items,
-                                    &V.on[k]);
+                    vis_item_offset(s.G, s.Wp, s.Lp, H, g, I.gi[k], I.gj[k], (int)(xy[k] & 0xFFFFu), (int)(xy[k] >> 16),
+                                    item_live(C, k, s.N * s.TW * s.TW), &V.on[k]);
     V.m[k] = *reinterpret_cast<const uint64_t*>(p);
     V.mo[k] = kVisSplit ? *reinterpret_cast<const uint64_t*>(p + kVisTiles * 8) : 0ull;
   }
@@ -905,12 +942,11 @@ template <class CT>
 __device__ __forceinline__ void vis_items_land(const State& s, const CT& C, Items<CT::KI>& I,
                                                const VisTiles<CT::KI>& V) {
   constexpr int KI = CT::KI, LPE = CT::LPE;
-  const int items = s.N * s.TW * s.TW;
 #pragma unroll
   for (int k = 0; k < KI; ++k) {
     const int idx = C.sub + k * LPE;
     I.mf[k] = I.mo[k] = 0;
-    if (idx < items) {
+    if (item_live(C, k, s.N * s.TW * s.TW)) {
       const uint64_t m = V.on[k] ? V.m[k] : 0ull;
       if constexpr (kVisSplit) {
         I.mf[k] = m;
@@ -954,8 +990,7 @@ template <class CT, int NS>
 __device__ __forceinline__ void vis_prefetch(const State& s, const CT& C, int g, const Items<CT::KI>& I,
                                              const uint32_t (&xy_after)[NS], uint32_t cell_own, bool blk,
                                              VisK<CT::KI>& P) {
-  constexpr int KI = CT::KI, LPE = CT::LPE, H = CT::SH::H;
-  const int items = s.N * s.TW * s.TW;
+  constexpr int KI = CT::KI, H = CT::SH::H;
   uint32_t pc[NS];
 #pragma unroll
   for (int i = 0; i < NS; ++i) {
@@ -965,12 +1000,19 @@ __device__ __forceinline__ void vis_prefetch(const State& s, const CT& C, int g,
   uint32_t fl = blk ? 0x100u : 0u;
 #pragma unroll
   for (int k = 0; k < KI; ++k) {
-    const uint32_t xa = pick_u<NS>(xy_after, I.a[k]), cell = pick_u<NS>(pc, I.a[k]);
+    uint32_t xa, cell;
+    if constexpr (CT::CARRY) {
+      xa = geo_pick<CT>(xy_after, C.sub, k);
+      cell = geo_pick<CT>(pc, C.sub, k);
+    } else {
+      xa = pick_u<NS>(xy_after, I.a[k]);
+      cell = pick_u<NS>(pc, I.a[k]);
+    }
     const int bx = ((int)(xa & 0xFFFFu) - s.H - 1) >> 3, by = ((int)(xa >> 16) - s.H - 1) >> 3;
     bool on;
     const char* p = reinterpret_cast<const char*>(s.vis_tab) +
                     vis_item_offset(s.G, s.Wp, s.Lp, H, g, bx + I.ti[k], by + I.tj[k], (int)(cell & 0xFFFFu),
-                                    (int)(cell >> 16), C.sub + k * LPE < items, &on);
+                                    (int)(cell >> 16), item_live(C, k, s.N * s.TW * s.TW), &on);
     P.m[k] = *reinterpret_cast<const uint64_t*>(p);
     P.cell[k] = cell;
     fl |= on ? 1u << k : 0u;
@@ -1461,7 +1503,7 @@ __device__ __forceinline__ void merge(const State& s, const CT& C, Items<CT::KI>
   constexpr int LPE = CT::LPE, EPW = CT::EPW, KI = CT::KI, NS = CT::NSM;
   const Lds<WT>& L = C.L;
   const int TW = s.TW;
-  const int items = s.N * TW * TW;
+  [[maybe_unused]] const int items = s.N * TW * TW;
   // compile-time agent count: every lower agent's block origin once, in
   // registers (broadcast LDS reads issued together)
   int BX[NS > 0 ? NS : 1], BY[NS > 0 ? NS : 1];
@@ -1517,7 +1559,7 @@ __device__ __forceinline__ void merge(const State& s, const CT& C, Items<CT::KI>
   for (int k = 0; k < KI; ++k) {
     const int idx = C.sub + k * LPE;
     I.nf[k] = I.no[k] = I.nu[k] = 0;
-    if (idx < items) {
+    if (item_live(C, k, items)) {
       const uint64_t fp = marks_in_regs ? I.mf[k] : L.fp[idx];
       const uint64_t op = obst_in_regs ? I.mo[k] : L.op[idx];
       const uint64_t f0 = I.f[k], o0 = I.o[k], u0 = I.u[k];  // first use of the mask loads
@@ -1543,11 +1585,21 @@ __device__ __forceinline__ void merge(const State& s, const CT& C, Items<CT::KI>
         // unconditionally (own tile when unused), no loop-carried branch
         // (an agent whose block misses the tile, or b >= a, reads the
         // slot's zero word)
+        // (CARRY: item k's agent is one of GEO::first(k) .. + AG - 1, so the
+        // rounds b >= first(k) + AG - 1 have no lane with a lower agent b and
+        // are not built, and b < first(k) is lower in every lane)
         uint64_t t[NS > 1 ? NS - 1 : 1];
 #pragma unroll
         for (int b = 0; b < NS - 1; ++b) {
+          if constexpr (CT::CARRY) {
+            if (b >= CT::GEO::first(k) + CT::GEO::AG - 1) {
+              t[b] = 0ull;
+              continue;
+            }
+          }
           const int bi = gi - BX[b], bj = gj - BY[b];
-          const bool use = b < a && (unsigned)bi < (unsigned)TW && (unsigned)bj < (unsigned)TW;
+          const bool lower = (CT::CARRY && b < CT::GEO::first(k)) ? true : b < a;
+          const bool use = lower && (unsigned)bi < (unsigned)TW && (unsigned)bj < (unsigned)TW;
           t[b] = *(use ? &L.fp[(b * TW + bi) * TW + bj] : &L.sc->zero);
         }
 #pragma unroll
@@ -1789,7 +1841,13 @@ __device__ __forceinline__ void store_tiles(const State& s, const CT& C, const I
   for (int k = 0; k < KI; ++k) {
     if (!I.in[k]) continue;
     // only obstacle marks can fall on an edge tile's cells beyond the map
-    const uint64_t no = I.no[k] & tile_in_grid(s, I.gi[k], I.gj[k]);
+    // (CARRY: `in` leaves tiles of the map only, so the last tile row's and
+    // column's masks do -- uniform, constants where the shape bakes the map in)
+    uint64_t no;
+    if constexpr (CT::CARRY)
+      no = I.no[k] & edge_clip(edge_row_mask(s.Wp), edge_col_mask(s.Lp), s.TR, s.TC, I.gi[k], I.gj[k]);
+    else
+      no = I.no[k] & tile_in_grid(s, I.gi[k], I.gj[k]);
     uint32_t gt;  // (in: the tile's own index)
     if constexpr (CT::KEEP_GT) gt = I.gt[k];
     else gt = tile_index24(s.TCS, I.gi[k], I.gj[k]);
@@ -1999,13 +2057,10 @@ __device__ __forceinline__ void reset_env(const State& s, const CT& C0, const in
   if constexpr (CT::VISTAB) {
     // the robots' cells are in L.x / L.y; the maps are known zero
     stage_load(s, C, g, /*load_masks=*/false, I);
-    int xk[KI], yk[KI];
+    uint32_t xyk[KI];
 #pragma unroll
-    for (int k = 0; k < KI; ++k) {
-      xk[k] = L.x[I.a[k]];
-      yk[k] = L.y[I.a[k]];
-    }
-    const VisTiles<KI> V = vis_items_load(s, C, g, I, xk, yk);
+    for (int k = 0; k < KI; ++k) xyk[k] = (uint32_t)L.x[I.a[k]] | ((uint32_t)L.y[I.a[k]] << 16);
+    const VisTiles<KI> V = vis_items_load(s, C, g, I, xyk);
     vis_items_land(s, C, I, V);
     sense_and_merge<CT, true>(s, C, I);
   } else {
@@ -2518,12 +2573,11 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
         const bool tgt_blk = (kVisPre && LOOP) ? blk_held : (!inb || ((tt >> tile_bit(tx, ty)) & 1ull));
         moves_front(s, C, F, tgt_blk, (uint32_t)tx | ((uint32_t)ty << 16), act, moved0, -s.pen, xy_after);
         if constexpr (CT::CARRY) xy_next = pick_u<NSM>(xy_after, ag);
-        int xk[KI], yk[KI];
+        uint32_t xyk[KI];
 #pragma unroll
         for (int k = 0; k < KI; ++k) {
-          const uint32_t xy = pick_u<NSM>(xy_after, I.a[k]);
-          xk[k] = (int)(xy & 0xFFFFu);
-          yk[k] = (int)(xy >> 16);
+          if constexpr (CT::CARRY) xyk[k] = geo_pick<CT>(xy_after, C.sub, k);
+          else xyk[k] = pick_u<NSM>(xy_after, I.a[k]);
         }
         // (VisK) the prefetched tiles where the moves gave every item's robot
         // of the wave's active slots its predicted cell
@@ -2532,7 +2586,7 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
           if (vis_held) {
             bool miss = false;
 #pragma unroll
-            for (int k = 0; k < KI; ++k) miss |= ((uint32_t)xk[k] | ((uint32_t)yk[k] << 16)) != VK.cell[k];
+            for (int k = 0; k < KI; ++k) miss |= xyk[k] != VK.cell[k];
             vis_hit = __ballot(miss) == 0;
           }
         }
@@ -2544,7 +2598,7 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
             V.on[k] = ((VK.fl >> k) & 1u) != 0;
           }
         } else {
-          V = vis_items_load(s, C, g0, I, xk, yk);
+          V = vis_items_load(s, C, g0, I, xyk);
           // the reloading arm's loads land inside it (a real s_waitcnt, as in
           // the head's loading arm): joined with one wait after the branch,
           // the predicted path would wait for its mask tiles there too

@@ -252,6 +252,21 @@ __host__ __device__ inline uint32_t tile_index(int TCS, int ti, int tj) {
          (uint32_t)(tj & 3);
 }
 
+// The cells of a map tile that lie inside the padded Wp x Lp grid, for a tile
+// of the map (0 <= gi < TR, 0 <= gj < TC): only the last tile row and the last
+// tile column hold cells beyond it, so two masks that depend on the map alone
+// -- the rows of the last tile row, the columns of the last tile column -- and
+// two compares give what tile_in_grid (mc_device.h) shifts out per tile
+__host__ __device__ constexpr uint64_t edge_row_mask(int Wp) {
+  return (Wp & 7) ? (1ull << (8 * (Wp & 7))) - 1ull : ~0ull;
+}
+__host__ __device__ constexpr uint64_t edge_col_mask(int Lp) {
+  return (Lp & 7) ? ((1ull << (Lp & 7)) - 1ull) * 0x0101010101010101ull : ~0ull;
+}
+__host__ __device__ constexpr uint64_t edge_clip(uint64_t rowm, uint64_t colm, int TR, int TC, int gi, int gj) {
+  return (gi == TR - 1 ? rowm : ~0ull) & (gj == TC - 1 ? colm : ~0ull);
+}
+
 // Lidar marks are made in "row form" (one u32/u64 per window row: the march's
 // address and bit are then one add and one shift), so a window row must fit
 // 64 bits: TW <= 8, i.e. H <= 27.  An agent's rows are 8*TW + 1 apart (odd:
@@ -449,7 +464,8 @@ using Dynamic = ShapeNone;  // nothing baked in: the generic kernels
 
 template <class SH>
 inline bool shape_matches(const State& s) {
-  return (SH::N == 0 || s.N == SH::N) && (SH::H == 0 || s.H == SH::H) &&
+  // (TW: the kernels of a compiled H derive a lane's items from window_tiles(H), ItemGeo)
+  return (SH::N == 0 || s.N == SH::N) && (SH::H == 0 || (s.H == SH::H && s.TW == window_tiles(SH::H))) &&
          (SH::NB == 0 || (s.sensor == 0 && s.nbeams == SH::NB)) &&
          (SH::EGO == 0 || (s.ego == SH::EGO && s.Lc == SH::LC && (s.dist != 0) == (SH::DS != 0))) &&
          (SH::KM == 0 || (s.sensor == 0 && s.beam_kmax == SH::KM)) &&

@@ -15,7 +15,16 @@ s_waitcnt, v_writelane / v_readlane (SGPR spill traffic, also in VALU).
 These are totals over EVERY path of the loop copy -- the in-step reset, the
 sentinel and the obs-only path included -- not the hot path: use them to see
 where a change moved instructions, and the SQ counters of tools/prof_config.py
---sq for what a step issues.  Needs no GPU."""
+--sq for what a step issues.
+
+    tools/isa_loop_count.py --blocks c2.s marl-coverage_amd/csrc/mc_env_step.h ShapeC2BV
+
+lists the loop copy's basic blocks instead, in layout order: the block's label
+(or +n for the fall-through block after a conditional branch), its counts per
+class, the functions its instructions come from, and where it ends -- the
+branch's mnemonic and target, or "falls through".  A path through the step is
+then a sum of rows: follow the targets.  Instruction classes only.
+Needs no GPU."""
 import collections
 import re
 import sys
@@ -50,8 +59,67 @@ def classify(op):
     return "other"
 
 
+def list_blocks(lines, fid, loop, fn, cols):
+    """The loop copy's basic blocks in layout order (--blocks)."""
+    cur, in_loop = ("?", 0), False
+    rows, blk = [], None
+
+    def start(label):
+        return {"label": label, "n": collections.Counter(), "fns": [], "end": "falls through"}
+
+    nfall = 0
+    for line in lines:
+        t = line.strip()
+        m = re.match(r"\.loc\s+(\d+)\s+(\d+)", t)
+        if m:
+            cur = (m.group(1), int(m.group(2)))
+            if cur[0] == fid and loop <= cur[1] < loop + 30:
+                in_loop = True
+            continue
+        if not in_loop:
+            continue
+        m = re.match(r"^(\.LBB\w+):", t)
+        if m:
+            if blk is not None:
+                rows.append(blk)
+            blk = start(m.group(1))
+            continue
+        if not t or t[0] in ".;" or t.endswith(":"):
+            continue
+        if blk is None:
+            blk = start("(loop entry)")
+        op = t.split()[0]
+        blk["n"][classify(op)] += 1
+        if op in ("v_writelane_b32", "v_readlane_b32"):
+            blk["n"][op[2:-4]] += 1
+        name = fn(cur[1]) if cur[0] == fid else "other files"
+        if name not in blk["fns"]:
+            blk["fns"].append(name)
+        if op.startswith("s_cbranch") or op in ("s_branch", "s_endpgm", "s_setpc_b64"):
+            target = t.split()[1] if len(t.split()) > 1 else ""
+            blk["end"] = (op + " " + target).strip()
+            rows.append(blk)
+            nfall += 1
+            blk = start("+%d" % nfall) if op.startswith("s_cbranch") else None
+    if blk is not None:
+        rows.append(blk)
+    print("%-14s" % "block" + "".join("%6s" % c[:5] for c in cols) + "  ends with / from")
+    total = collections.Counter()
+    for b in rows:
+        if not b["fns"]:  # an empty fall-through stub
+            continue
+        print("%-14s" % b["label"] + "".join("%6d" % b["n"][k] for k in cols) + "  " + b["end"] + "  [" +
+              ", ".join(b["fns"]) + "]")
+        total += b["n"]
+    print("%-14s" % "TOTAL" + "".join("%6d" % total[k] for k in cols))
+
+
 def main():
-    asm, header, kernel = sys.argv[1:4]
+    args = sys.argv[1:]
+    blocks = "--blocks" in args
+    if blocks:
+        args.remove("--blocks")
+    asm, header, kernel = args[:3]
     starts = function_starts(header)
     loop = next((st for st, n in starts if n == "loop_body"), 0)
 
@@ -75,6 +143,9 @@ def main():
     end = next(i for i in range(beg, len(lines)) if lines[i].strip().startswith(".Lfunc_end"))
     cur, in_loop = ("?", 0), False
     agg = collections.defaultdict(collections.Counter)
+    cols = ["VALU", "SALU", "SMEM", "LDS", "VMEM", "wait", "writelane", "readlane"]
+    if blocks:
+        return list_blocks(lines[beg:end], fid, loop, fn, cols)
     for line in lines[beg:end]:
         t = line.strip()
         m = re.match(r"\.loc\s+(\d+)\s+(\d+)", t)
@@ -90,7 +161,6 @@ def main():
         agg[name][classify(op)] += 1
         if op in ("v_writelane_b32", "v_readlane_b32"):
             agg[name][op[2:-4]] += 1
-    cols = ["VALU", "SALU", "SMEM", "LDS", "VMEM", "wait", "writelane", "readlane"]
     print("%-22s" % "function" + "".join("%10s" % c for c in cols))
     total = collections.Counter()
     for name, c in sorted(agg.items(), key=lambda kv: -kv[1]["VALU"]):
