@@ -254,6 +254,14 @@ __device__ __forceinline__ int bcast(const CT& C, int v, int i) {
   else return __shfl(v, C.lane0 + i);
 }
 
+// one env per workgroup: the env's flags are uniform -- made scalar
+// (readfirstlane), their branches are scalar branches instead of lane masks
+// kept in SGPR pairs
+template <class CT>
+__device__ __forceinline__ int uniform(int v) {
+  return CT::EPW == 1 ? __builtin_amdgcn_readfirstlane(v) : v;
+}
+
 // ballot restricted to this env's slot (bit j = lane lane0 + j)
 template <class CT>
 __device__ __forceinline__ uint64_t slot_ballot(const CT& C, bool p) {
@@ -2344,6 +2352,298 @@ constexpr int env_min_waves() {
   return SH::N == 16 ? 4 : 1;
 }
 
+// updateRobotPos' direction index of a move by (dx, dy): dist_pre's terms 1..4, 0 for a robot that stayed
+__device__ __forceinline__ int move_dir(int dx, int dy) {
+  return dx == 1 ? 1 : (dy == 1 ? 2 : (dx == -1 ? 3 : (dy == -1 ? 4 : 0)));
+}
+
+// The phases of env_step below take N, the agent count as the step read it
+// before its first reload_state (the generic kernels keep it in a register).
+
+// ---- the state commit of a step or reset: positions, moved, and the
+// dist_reward records of the lane's agent.  was_reset: by reset_req or by a
+// sentinel; chd / chb: the agent's top-cell cache as round trip 1 loaded it
+template <class CT>
+__device__ __forceinline__ void commit_state(const State& s, const CT& C, const int N, const bool was_reset,
+                                             const int4& chd, const int2& chb) {
+  constexpr bool O32 = CT::O32;
+  const Lds<typename CT::WT>& L = C.L;
+  const int e = C.e;
+  if (C.sub < N)
+    el<O32>(reinterpret_cast<int2*>(s.pos), (uint32_t)e * (uint32_t)N + C.sub) = make_int2(L.x[C.sub], L.y[C.sub]);
+  if (C.sub == 0) el<O32>(s.rec, e).moved = L.sc->moved;
+  // dist_reward: a reset map, or one whose witness got closer than M,
+  // has an unknown M now (recomputed by the full transform, mc_dist.hip)
+  if (s.dist && C.sub < N &&
+      (was_reset || L.sc->do_reset || ((L.sc->dist_hit >> C.sub) & 1ull)))
+    s.dist_mw[((size_t)e * N + C.sub) * 2] = -1;
+  if (s.dist_ch && C.sub < N) {
+    int* hp = s.dist_ch + ((size_t)e * N + C.sub) * 8;
+    if (was_reset || L.sc->do_reset) {
+      hp[0] = -1;  // the map was cleared: the cached cells' d are stale
+    } else if (chd.x > 0) {  // every newly covered cell lies in the sensing window
+      const int x = L.x[C.sub], y = L.y[C.sub], H = s.H;
+      *reinterpret_cast<int4*>(hp) = make_int4(chd.x, chd.y, min(chd.z, x - H), min(chd.w, y - H));
+      *reinterpret_cast<int2*>(hp + 4) = make_int2(max(chb.x, x + H), max(chb.y, y + H));
+    }
+  }
+}
+
+// ---- the full transform's work list (mc_dist.hip launch_dist_listed): one
+// atomic per env slot of the wave on its env's shard (e % kListShards,
+// spread over kListShards lines: early after a reset nearly every env
+// appends, ~8k returning atomics per step on one address), the slot's
+// entries at consecutive places of the shard.  me: the lane's agent goes there
+template <class CT>
+__device__ __forceinline__ void dist_list_append(const State& s, const CT& C, const int N, const bool me) {
+  constexpr int LPE = CT::LPE;
+  const int e = C.e;
+  const uint64_t m = __ballot(me);
+  if (m) {
+    const int lane = C.lane;
+    const uint64_t slotm = LPE >= 64 ? ~0ull : (low_mask(LPE) << (lane & ~(LPE - 1) & 63));
+    const uint64_t ms = m & slotm;
+    if (ms) {
+      const int leader = __ffsll((unsigned long long)ms) - 1;
+      const uint32_t sh = (uint32_t)e % (uint32_t)kListShards;
+      uint32_t base = 0;
+      if (lane == leader) base = atomicAdd(s.dist_shc + sh * kShardStride, (uint32_t)__popcll(ms));
+      base = (uint32_t)__shfl((int)base, leader);
+      if (me)
+        s.dist_cnt[5 + sh * s.dist_cap + base + __popcll(ms & ((1ull << lane) - 1ull))] =
+            (uint32_t)e * (uint32_t)N + (uint32_t)C.sub;
+    }
+  }
+  if (s.dist_full && blockIdx.x == 0 && threadIdx.x == 0) {  // the last step's full list is done
+    s.dist_full[2] = s.dist_full[0];
+    s.dist_full[0] = 0;
+  }
+}
+
+// ---- updateCommmunicationGraph (:374-391) of the slot's env
+template <class CT>
+__device__ __forceinline__ void write_adj(const State& s, const CT& C, const int N, uint8_t* adj_out) {
+  const Lds<typename CT::WT>& L = C.L;
+  uint8_t* ad = adj_out + (size_t)C.e * N * N;
+  for (int idx = C.sub; idx < N * N; idx += CT::LPE) {
+    const int i = idx / N, j = idx - i * N;
+    const int dx = abs(L.x[i] - L.x[j]), dy = abs(L.y[i] - L.y[j]);
+    ad[idx] = (max(dx, dy) <= s.comm_r) ? 1 : 0;
+  }
+}
+
+// The cell a robot at (x, y) moves to with action byte act (its own cell for a
+// byte that is no move), whether the map holds it, its grid < 0 tile and the
+// blocked test: the moves of the register front and the next step's prediction
+struct Target {
+  int tx, ty;
+  bool inb;
+  __device__ __forceinline__ uint32_t xy() const { return (uint32_t)tx | ((uint32_t)ty << 16); }
+};
+__device__ __forceinline__ Target target_of(const State& s, int x, int y, int act) {
+  const int dx = (act == 0) - (act == 2), dy = (act == 1) - (act == 3);
+  const int tx = x + dx, ty = y + dy;
+  return {tx, ty, (unsigned)tx < (unsigned)s.Wp && (unsigned)ty < (unsigned)s.Lp};
+}
+template <bool O32>
+__device__ __forceinline__ uint64_t target_tile(const State& s, int g, const Target& T) {
+  return ld_tile<O32>(s.grid_neg, __umul24((uint32_t)g, (uint32_t)s.MT) +
+                                      tile_index24(s.TCS, T.inb ? T.tx >> 3 : 0, T.inb ? T.ty >> 3 : 0));
+}
+__device__ __forceinline__ bool target_blocked(const Target& T, uint64_t tile) {
+  return !T.inb || ((tile >> tile_bit(T.tx, T.ty)) & 1ull);
+}
+
+// The env's counters around the reward: as the step read them going in, as
+// it stored them coming out
+struct Counters {
+  uint32_t free_cnt, vis_cnt;
+  int currstep;
+  double done_thresh;
+};
+
+// ---- reward and done: every lane of the slot computes them (the same
+// values: no broadcast round trip or barrier before the stores); lane 0
+// stores.  cn: the counters before the step, and after it on return; dpre0 /
+// dprek: the lane's agent's PRE terms (kPrePrefetch).  Returns do_reset
+template <class CT>
+__device__ __forceinline__ bool reward_done(const State& s, const EnvIO& io, const CT& C, const int N, Counters& cn,
+                                            const float dpre0, const float dprek, const int numfree) {
+  constexpr bool O32 = CT::O32, kPrePrefetch = CT::kPrePrefetch;
+  const Lds<typename CT::WT>& L = C.L;
+  const int e = C.e;
+  Scal* c = L.sc;
+  const uint32_t fc = cn.free_cnt + c->cnt_free;
+  const uint32_t vc = cn.vis_cnt + c->cnt_vis;
+  const int cs = cn.currstep + 1;                         // :154
+  // observe() :206-258 returns the float32 sum of the agents' distance
+  // terms (dist_reward, agent order) plus the union delta (float64)
+  // (only lane 0's value is stored: the agents' terms are in the slot's
+  // first lanes, N <= 64, and are summed in agent order)
+  float dsum = 0.0f;
+  if (s.dist) {
+    if constexpr (kPrePrefetch) {
+      const float term = dist_value(dprek, dpre0);  // :222-223,239-240
+      for (int i = 0; i < N; ++i)
+        dsum = __fadd_rn(dsum, __builtin_bit_cast(float, bcast(C, __builtin_bit_cast(int, term), i)));
+    } else {
+      for (int i = 0; i < N; ++i) {
+        const int dx = L.x[i] - L.x0[i], dy = L.y[i] - L.y0[i];
+        const int k = move_dir(dx, dy);
+        const float* pr = s.dist_pre + ((size_t)e * N + i) * 8;
+        dsum = __fadd_rn(dsum, dist_value(pr[1 + k], pr[0]));  // :222-223,239-240
+      }
+    }
+  }
+  const double obs_reward = (double)dsum + (double)c->cnt_vis;
+  double r = c->pen + obs_reward;                        // :120,132-151
+  double dt = cn.done_thresh;
+  const double thr = (1.0 < dt) ? 1.0 : dt;              // min(done_thresh, 1)
+  // pc = count/numfree (:552), correctly rounded; thr <= pc.  With thr
+  // == 1 (the default) the test is fc >= numfree exactly (counts are
+  // < 2^24: a quotient below 1 rounds below 1), so the float64 divide
+  // runs only when the threshold or the episode record needs it.  A
+  // grid with no cell > 0 takes the division: 0/0 = NaN is never covered,
+  // as in the reference
+  const bool exact1 = thr == 1.0 && numfree > 0;
+  double pc = 0.0;
+  if (!exact1) pc = (double)fc / (double)numfree;
+  const bool covered = exact1 ? fc >= (uint32_t)numfree : thr <= pc;
+  if (covered) r += s.term;                              // :156-157
+  bool done = false;
+  if (covered) { dt += s.dincr; done = true; }           // :540-543
+  else if (cs == s.maxsteps) done = true;                // :544-545
+  const bool do_reset = uniform<CT>((int)(done && s.auto_reset)) != 0;
+  if (C.sub == 0) {
+    el<O32>(io.reward_out, e) = r;
+    el<O32>(io.done_out, e) = done ? 1 : 0;
+    if (done) {  // the episode record (Utils/utils.py:138-141)
+      el<O32>(s.ep_pc, e) = exact1 ? (double)fc / (double)numfree : pc;
+      el<O32>(s.ep_len, e) = cs;
+    }
+    rec_store_counts(el<O32>(s.rec, e), dt, fc, vc, cs);
+    c->do_reset = do_reset ? 1 : 0;
+  }
+  cn = {fc, vc, cs, dt};
+  return do_reset;
+}
+
+// ---- dist_reward: the POST terms of the maps whose M is still known (the
+// others, and a reset env's, go to the full transform's list: returns whether
+// the lane's agent does)
+template <class CT>
+__device__ __forceinline__ bool dist_post(const State& s, const CT& C, const int N, const bool do_reset) {
+  using SH = typename CT::SH;
+  constexpr int NT = CT::NT, LPE = CT::LPE;
+  constexpr bool kPrePrefetch = CT::kPrePrefetch;
+  const Lds<typename CT::WT>& L = C.L;
+  const uint64_t skip = do_reset ? ~0ull : L.sc->dist_hit;  // (and every agent with M < 0)
+  // dist_window overwrites dist_pre with the POST terms; without the
+  // prefetch every lane of the slot read all agents' PRE terms in the
+  // reward above, and in a multi-wave slot another wave may still be
+  // there: every wave passes the reward before any POST store
+  if constexpr (NT > 64 && !kPrePrefetch) __syncthreads();
+  if (MC_ABL != 1) {
+    // (tried, round 5: one lane per (agent, target row) growing the
+    // row's covered set by a bit-parallel dilation -- 83.6 against 81.7
+    // us at the C5 steady state, profiles/r5/win/; removed)
+    if constexpr (LPE % 32 == 0) {
+      if constexpr (SH::N > 0 && SH::N <= 64) {
+        if (5 + s.E * s.E <= 32) dist_window_am2(s, C, skip);
+        else dist_window(s, C, skip);
+      } else {
+        if (5 + s.E * s.E <= 32) dist_window_am(s, C, skip);
+        else dist_window(s, C, skip);
+      }
+    } else {
+      dist_window(s, C, skip);
+    }
+  }
+  __syncthreads();
+  return C.sub < N && ((((skip | L.sc->dist_fail) >> C.sub) & 1ull) || L.dm[C.sub] < 0);
+}
+
+// ---- the moves of the plain round trip 2, after its barrier: the first wave
+// of the slot moves the robots (lane 0 publishes); the other waves of a
+// multi-wave workgroup only wait at the barrier
+// (C5, 16 agents: moves_regs took 17.7k vs 7.3k cycles per wave -- the
+// every-lane replay of 256 position compares outweighs the broadcasts;
+// the loop on the scalar unit from v_readlane copies, 111.3 vs 107.8 us
+// per env kernel, profiles/r4/c5_grid/)
+template <class CT>
+__device__ __forceinline__ void moves_plain(const State& s, const CT& C) {
+  using SH = typename CT::SH;
+  if constexpr (SH::N > 0 && SH::N <= 8) {
+    if (CT::NT == 64 || C.sub < 64) moves_regs(s, C, -s.pen);
+  } else if constexpr (SH::N > 8 && CT::EPW == 1) {
+    if (C.sub < 64) moves_par(s, C, -s.pen);
+  } else if (C.sub < 64) {
+    moves(s, C, -s.pen);
+  }
+  __syncthreads();
+}
+
+// ---- sentinel step without auto-reset / env left out of a partial reset:
+// obs of the current state only (dec_grid_rl.py:104-107,160).  Only the
+// old free / obstacle tiles are needed (fold / oold): no row or column
+// plane is scattered.  With the fan march the column planes overlay
+// fold / oold (carve), and a multi-wave slot's column-byte stores would
+// race with another wave's stage_fold stores.  fc, cs: the env's counters, for
+// a sentinel's episode record.  Returns whether the lane's agent goes to the
+// full transform's list
+template <class CT>
+__device__ __forceinline__ bool obs_only(const State& s, const EnvIO& io, const CT& C, const int N, const int g,
+                                         const bool sentinel, const uint32_t fc, const int cs) {
+  Items<CT::KI> I;
+  stage_load(s, C, g, true, I);
+  stage_fold(s, C, I);
+  // unchanged maps keep their dist terms; an unknown M (a state upload)
+  // needs the full transform
+  const bool dlist = s.dist && C.sub < N && C.L.dm[C.sub] < 0;
+  if (C.sub == 0 && sentinel) sentinel_done(s, io, C.e, g, fc, cs);
+  // (CARRY: the grid tiles stage_load read for nothing land here, inside the
+  // arm.  It is laid out ahead of the active path, and a load it left in
+  // flight made that path's moves wait for all but its newest loads, the
+  // last step's stores among them)
+  if constexpr (CT::CARRY) __builtin_amdgcn_s_waitcnt(0x0F70);
+  return dlist;
+}
+
+// (VisK) the record tiles of the items' robots' cells xyk: the prefetched ones
+// where the moves gave every item's robot of the wave's active slots its
+// predicted cell (vis_held: the loop copy with a carried head may hold the
+// last step's), else loaded now
+template <class CT, bool LOOP>
+__device__ __forceinline__ void vis_take_or_load(const State& s, const CT& C, const int g, const Items<CT::KI>& I,
+                                                 const uint32_t (&xyk)[CT::KI], [[maybe_unused]] const bool vis_held,
+                                                 [[maybe_unused]] const VisK<CT::KI>& VK, VisTiles<CT::KI>& V) {
+  constexpr int KI = CT::KI;
+  constexpr bool kVisPre = CT::CARRY && !kVisSplit;
+  bool vis_hit = false;
+  if constexpr (kVisPre && LOOP) {
+    if (vis_held) {
+      bool miss = false;
+#pragma unroll
+      for (int i = 0; i < KI; ++i) miss |= xyk[i] != VK.cell[i];
+      vis_hit = __ballot(miss) == 0;
+    }
+  }
+  if ((kVisPre && LOOP) && vis_hit) {
+#pragma unroll
+    for (int i = 0; i < KI; ++i) {
+      V.m[i] = VK.m[i];
+      V.mo[i] = 0ull;
+      V.on[i] = ((VK.fl >> i) & 1u) != 0;
+    }
+  } else {
+    V = vis_items_load(s, C, g, I, xyk);
+    // the reloading arm's loads land inside it (a real s_waitcnt, as in
+    // the head's loading arm): joined with one wait after the branch,
+    // the predicted path would wait for its mask tiles there too
+    if constexpr (kVisPre && LOOP) __builtin_amdgcn_s_waitcnt(0x0F70);
+  }
+}
+
 // One step (or the reset) of the slot's env: step k of the launch, with io the
 // launch's buffers as step k sees them (io_at_step).  `valid`: the slot has an
 // env (a short last workgroup's idle slot writes nothing, in any step).
@@ -2469,12 +2769,8 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
     for (int q = 0; q < CT::RPW; q += 4) asm volatile("" ::"v"(C.rp[q]));
   }
   const int act = is_step ? act_raw : 255;
-  // one env per workgroup: the env's flags are uniform -- made scalar
-  // (readfirstlane), their branches are scalar branches instead of lane masks
-  // kept in SGPR pairs
-  auto uni = [](int v) { return EPW == 1 ? __builtin_amdgcn_readfirstlane(v) : v; };
-  const int act0 = uni(is_step ? act0_raw : 0);  // agent 0's byte: the sentinel
-  const int req = uni(io.env_mask != nullptr ? req_raw : 1);
+  const int act0 = uniform<CT>(is_step ? act0_raw : 0);  // agent 0's byte: the sentinel
+  const int req = uniform<CT>(io.env_mask != nullptr ? req_raw : 1);
 
   const bool sentinel = valid && is_step && act0 == 255;
   const bool reset_req = valid && !is_step && req != 0;
@@ -2540,9 +2836,7 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
       // origins and moves from registers (front_regs)
       Front<NSM> F;
       front_regs(s, C, p0.x, p0.y, act, F);
-      const int dx = (act == 0) - (act == 2), dy = (act == 1) - (act == 3);
-      const int tx = p0.x + dx, ty = p0.y + dy;
-      const bool inb = (unsigned)tx < (unsigned)s.Wp && (unsigned)ty < (unsigned)s.Lp;
+      const Target T = target_of(s, p0.x, p0.y, act);
       uint64_t tt = 0;
       [[maybe_unused]] bool blk_held = false;
       if constexpr (kVisPre && LOOP) {
@@ -2551,13 +2845,11 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
         if (vis_held) {
           blk_held = (VK.fl & 0x100u) != 0;
         } else {
-          tt = ld_tile<O32>(s.grid_neg, __umul24((uint32_t)g0, (uint32_t)s.MT) +
-                                            tile_index24(s.TCS, inb ? tx >> 3 : 0, inb ? ty >> 3 : 0));
-          blk_held = !inb || ((tt >> tile_bit(tx, ty)) & 1ull);
+          tt = target_tile<O32>(s, g0, T);
+          blk_held = target_blocked(T, tt);
         }
       } else {
-        tt = ld_tile<O32>(s.grid_neg, __umul24((uint32_t)g0, (uint32_t)s.MT) +
-                                          tile_index24(s.TCS, inb ? tx >> 3 : 0, inb ? ty >> 3 : 0));
+        tt = target_tile<O32>(s, g0, T);
       }
       if constexpr (CT::VISTAB) {
         // ... and after the moves every item's tile of the record of its
@@ -2570,44 +2862,19 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
           act_next = el<O32>(an, eN + ag);
           act0_next = el<O32>(an, eN);
         }
-        const bool tgt_blk = (kVisPre && LOOP) ? blk_held : (!inb || ((tt >> tile_bit(tx, ty)) & 1ull));
-        moves_front(s, C, F, tgt_blk, (uint32_t)tx | ((uint32_t)ty << 16), act, moved0, -s.pen, xy_after);
+        const bool tgt_blk = (kVisPre && LOOP) ? blk_held : target_blocked(T, tt);
+        moves_front(s, C, F, tgt_blk, T.xy(), act, moved0, -s.pen, xy_after);
         if constexpr (CT::CARRY) xy_next = pick_u<NSM>(xy_after, ag);
         uint32_t xyk[KI];
 #pragma unroll
-        for (int k = 0; k < KI; ++k) {
-          if constexpr (CT::CARRY) xyk[k] = geo_pick<CT>(xy_after, C.sub, k);
-          else xyk[k] = pick_u<NSM>(xy_after, I.a[k]);
+        for (int i = 0; i < KI; ++i) {  // (k is the step of the launch)
+          if constexpr (CT::CARRY) xyk[i] = geo_pick<CT>(xy_after, C.sub, i);
+          else xyk[i] = pick_u<NSM>(xy_after, I.a[i]);
         }
-        // (VisK) the prefetched tiles where the moves gave every item's robot
-        // of the wave's active slots its predicted cell
-        bool vis_hit = false;
-        if constexpr (kVisPre && LOOP) {
-          if (vis_held) {
-            bool miss = false;
-#pragma unroll
-            for (int k = 0; k < KI; ++k) miss |= xyk[k] != VK.cell[k];
-            vis_hit = __ballot(miss) == 0;
-          }
-        }
-        if ((kVisPre && LOOP) && vis_hit) {
-#pragma unroll
-          for (int k = 0; k < KI; ++k) {
-            V.m[k] = VK.m[k];
-            V.mo[k] = 0ull;
-            V.on[k] = ((VK.fl >> k) & 1u) != 0;
-          }
-        } else {
-          V = vis_items_load(s, C, g0, I, xyk);
-          // the reloading arm's loads land inside it (a real s_waitcnt, as in
-          // the head's loading arm): joined with one wait after the branch,
-          // the predicted path would wait for its mask tiles there too
-          if constexpr (kVisPre && LOOP) __builtin_amdgcn_s_waitcnt(0x0F70);
-        }
+        vis_take_or_load<CT, LOOP>(s, C, g0, I, xyk, vis_held, VK, V);
       } else {
         stage_load(s, C, g0, true, I, &F);
-        moves_front(s, C, F, !inb || ((tt >> tile_bit(tx, ty)) & 1ull), (uint32_t)tx | ((uint32_t)ty << 16), act,
-                    moved0, -s.pen);
+        moves_front(s, C, F, target_blocked(T, tt), T.xy(), act, moved0, -s.pen);
         stage_scatter(s, C, I);
       }
     } else if constexpr (EARLY) {
@@ -2615,18 +2882,14 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
       // moves the robots from registers (front_regs / moves_front: lane i
       // holds robot i, its target-cell grid tile loaded first) while the
       // staged tiles are in flight; the other waves only stage
-      const int dx = (act == 0) - (act == 2), dy = (act == 1) - (act == 3);
-      const int tx = p0.x + dx, ty = p0.y + dy;
-      const bool inb = (unsigned)tx < (unsigned)s.Wp && (unsigned)ty < (unsigned)s.Lp;
-      const uint64_t tt = ld_tile<O32>(s.grid_neg, __umul24((uint32_t)g0, (uint32_t)s.MT) +
-                                                       tile_index24(s.TCS, inb ? tx >> 3 : 0, inb ? ty >> 3 : 0));
+      const Target T = target_of(s, p0.x, p0.y, act);
+      const uint64_t tt = target_tile<O32>(s, g0, T);
       stage_load(s, C, g0, true, I);
       STAMP(15);  // loads issued (the first wave's moves follow)
       if (C.sub < 64) {
         Front<NSM> F;
         front_regs(s, C, p0.x, p0.y, act, F);
-        moves_front(s, C, F, !inb || ((tt >> tile_bit(tx, ty)) & 1ull), (uint32_t)tx | ((uint32_t)ty << 16), act,
-                    moved0, -s.pen);
+        moves_front(s, C, F, target_blocked(T, tt), T.xy(), act, moved0, -s.pen);
       }
       stage_scatter(s, C, I);
     } else {
@@ -2643,22 +2906,7 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
     reload_state<SH, EPW, LOOP>(s, io, k);
     // (the same loop on the scalar unit, robots read by v_readlane, was
     // slower: 10.17 vs 9.83 us at C2 -- +178 SALU for -17 VALU per wave)
-    if constexpr (!FRONT && !EARLY) {  // (FRONT, EARLY: moved during round trip 2)
-      // the first wave of the slot moves the robots (lane 0 publishes); the
-      // other waves of a multi-wave workgroup only wait at the barrier
-      // (C5, 16 agents: moves_regs took 17.7k vs 7.3k cycles per wave -- the
-      // every-lane replay of 256 position compares outweighs the broadcasts;
-      // the loop on the scalar unit from v_readlane copies, 111.3 vs 107.8 us
-      // per env kernel, profiles/r4/c5_grid/)
-      if constexpr (SH::N > 0 && SH::N <= 8) {
-        if (NT == 64 || C.sub < 64) moves_regs(s, C, -s.pen);
-      } else if constexpr (SH::N > 8 && EPW == 1) {
-        if (C.sub < 64) moves_par(s, C, -s.pen);
-      } else if (C.sub < 64) {
-        moves(s, C, -s.pen);
-      }
-      __syncthreads();
-    }
+    if constexpr (!FRONT && !EARLY) moves_plain(s, C);  // (FRONT, EARLY: moved during round trip 2)
     STAMP(3);
     reload_state<SH, EPW, LOOP>(s, io, k);
     // dist_reward: lane i < N loads its agent's PRE terms (the last step's
@@ -2667,20 +2915,18 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
     // one env per workgroup: the env's counters re-read here (they land
     // during the sensing) rather than kept from round trip 1 in SGPRs,
     // which spilled (nothing writes them before the reward)
-    uint32_t free_old_r = free_old, vis_old_r = vis_old;
-    int currstep_r = currstep0;
-    double dthresh_r = dthresh0;
+    Counters cn = {free_old, vis_old, currstep0, dthresh0};
     if constexpr (EPW == 1 && !CT::CARRY) {  // (CARRY: they are VGPRs of the head)
       const RecLo rl = rec_lo(el<O32>(s.rec, e));
-      free_old_r = rl.free_cnt;
-      vis_old_r = rl.vis_cnt;
-      currstep_r = el<O32>(s.rec, e).currstep;
-      dthresh_r = rl.done_thresh;
+      cn.free_cnt = rl.free_cnt;
+      cn.vis_cnt = rl.vis_cnt;
+      cn.currstep = el<O32>(s.rec, e).currstep;
+      cn.done_thresh = rl.done_thresh;
     }
     float dpre0 = 0.0f, dprek = 0.0f;
     if (kPrePrefetch && s.dist && C.sub < N) {
       const int dx = L.x[C.sub] - L.x0[C.sub], dy = L.y[C.sub] - L.y0[C.sub];
-      const int k = dx == 1 ? 1 : (dy == 1 ? 2 : (dx == -1 ? 3 : (dy == -1 ? 4 : 0)));
+      const int k = move_dir(dx, dy);
       const float* pr = s.dist_pre + ((size_t)e * N + C.sub) * 8;
       dpre0 = pr[0];
       dprek = pr[1 + k];
@@ -2690,126 +2936,38 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
     // after this step's moves and the next action byte (landed with the record
     // tiles: loads return in order); its grid tile lands during the merge and
     // the reward, and is used after the tile stores (vis_prefetch)
-    [[maybe_unused]] int ntx = 0, nty = 0;
-    [[maybe_unused]] bool ninb = false;
+    [[maybe_unused]] Target Tn = {0, 0, false};
     [[maybe_unused]] uint64_t tn = 0;
     if constexpr (kVisPre) {
       if (vis_more) {
-        const int an = (int)act_next;
-        ntx = (int)(xy_next & 0xFFFFu) + ((an == 0) - (an == 2));
-        nty = (int)(xy_next >> 16) + ((an == 1) - (an == 3));
-        ninb = (unsigned)ntx < (unsigned)s.Wp && (unsigned)nty < (unsigned)s.Lp;
-        tn = ld_tile<O32>(s.grid_neg, __umul24((uint32_t)g0, (uint32_t)s.MT) +
-                                          tile_index24(s.TCS, ninb ? ntx >> 3 : 0, ninb ? nty >> 3 : 0));
+        Tn = target_of(s, (int)(xy_next & 0xFFFFu), (int)(xy_next >> 16), (int)act_next);
+        tn = target_tile<O32>(s, g0, Tn);
       }
     }
     sense_and_merge<CT, CT::VISTAB>(s, C, I);
     __syncthreads();
     STAMP(5);
     reload_state<SH, EPW, LOOP>(s, io, k);
-    // every lane of the slot computes the reward and done (the same values:
-    // no broadcast round trip or barrier before the stores); lane 0 stores
-    bool do_reset;
-    {
-      Scal* c = L.sc;
-      const uint32_t fc = free_old_r + c->cnt_free;
-      const uint32_t vc = vis_old_r + c->cnt_vis;
-      const int cs = currstep_r + 1;                         // :154
-      // observe() :206-258 returns the float32 sum of the agents' distance
-      // terms (dist_reward, agent order) plus the union delta (float64)
-      // (only lane 0's value is stored: the agents' terms are in the slot's
-      // first lanes, N <= 64, and are summed in agent order)
-      float dsum = 0.0f;
-      if (s.dist) {
-        if constexpr (kPrePrefetch) {
-          const float term = dist_value(dprek, dpre0);  // :222-223,239-240
-          for (int i = 0; i < N; ++i)
-            dsum = __fadd_rn(dsum, __builtin_bit_cast(float, bcast(C, __builtin_bit_cast(int, term), i)));
-        } else {
-          for (int i = 0; i < N; ++i) {
-            const int dx = L.x[i] - L.x0[i], dy = L.y[i] - L.y0[i];
-            const int k = dx == 1 ? 1 : (dy == 1 ? 2 : (dx == -1 ? 3 : (dy == -1 ? 4 : 0)));
-            const float* pr = s.dist_pre + ((size_t)e * N + i) * 8;
-            dsum = __fadd_rn(dsum, dist_value(pr[1 + k], pr[0]));  // :222-223,239-240
-          }
-        }
-      }
-      const double obs_reward = (double)dsum + (double)c->cnt_vis;
-      double r = c->pen + obs_reward;                        // :120,132-151
-      double dt = dthresh_r;
-      const double thr = (1.0 < dt) ? 1.0 : dt;              // min(done_thresh, 1)
-      // pc = count/numfree (:552), correctly rounded; thr <= pc.  With thr
-      // == 1 (the default) the test is fc >= numfree exactly (counts are
-      // < 2^24: a quotient below 1 rounds below 1), so the float64 divide
-      // runs only when the threshold or the episode record needs it.  A
-      // grid with no cell > 0 takes the division: 0/0 = NaN is never covered,
-      // as in the reference
-      const bool exact1 = thr == 1.0 && numfree > 0;
-      double pc = 0.0;
-      if (!exact1) pc = (double)fc / (double)numfree;
-      const bool covered = exact1 ? fc >= (uint32_t)numfree : thr <= pc;
-      if (covered) r += s.term;                              // :156-157
-      bool done = false;
-      if (covered) { dt += s.dincr; done = true; }           // :540-543
-      else if (cs == s.maxsteps) done = true;                // :544-545
-      do_reset = uni((int)(done && s.auto_reset)) != 0;
-      if (C.sub == 0) {
-        el<O32>(io.reward_out, e) = r;
-        el<O32>(io.done_out, e) = done ? 1 : 0;
-        if (done) {  // the episode record (Utils/utils.py:138-141)
-          el<O32>(s.ep_pc, e) = exact1 ? (double)fc / (double)numfree : pc;
-          el<O32>(s.ep_len, e) = cs;
-        }
-        rec_store_counts(el<O32>(s.rec, e), dt, fc, vc, cs);
-        c->do_reset = do_reset ? 1 : 0;
-      }
-      if constexpr (CT::CARRY) {
-        // the head of the next step: what this step stores, and will store
-        // below, kept in registers as well.  (A reset leaves `ok` clear: the
-        // next step loads what reset_env wrote.)
-        const uint64_t mv = c->moved;
-        Hd.xy = xy_next;
-        Hd.act = act_next;
-        Hd.act0 = act0_next;
-        Hd.numfree = (uint32_t)numfree;
-        Hd.moved_lo = (uint32_t)mv;
-        Hd.moved_hi = (uint32_t)(mv >> 32);
-        Hd.free_cnt = fc;
-        Hd.vis_cnt = vc;
-        Hd.currstep = (uint32_t)cs;
-        Hd.dt_lo = (uint32_t)__double2loint(dt);
-        Hd.dt_hi = (uint32_t)__double2hiint(dt);
-        Hd.ok = do_reset ? 0u : 1u;
-      }
+    const bool do_reset = reward_done(s, io, C, N, cn, dpre0, dprek, numfree);
+    if constexpr (CT::CARRY) {
+      // the head of the next step: what this step stores, and will store
+      // below, kept in registers as well.  (A reset leaves `ok` clear: the
+      // next step loads what reset_env wrote.)
+      const uint64_t mv = L.sc->moved;
+      Hd.xy = xy_next;
+      Hd.act = act_next;
+      Hd.act0 = act0_next;
+      Hd.numfree = (uint32_t)numfree;
+      Hd.moved_lo = (uint32_t)mv;
+      Hd.moved_hi = (uint32_t)(mv >> 32);
+      Hd.free_cnt = cn.free_cnt;
+      Hd.vis_cnt = cn.vis_cnt;
+      Hd.currstep = (uint32_t)cn.currstep;
+      Hd.dt_lo = (uint32_t)__double2loint(cn.done_thresh);
+      Hd.dt_hi = (uint32_t)__double2hiint(cn.done_thresh);
+      Hd.ok = do_reset ? 0u : 1u;
     }
-    // dist_reward: the POST terms of the maps whose M is still known (the
-    // others, and a reset env's, go to the full transform's list)
-    if (s.dist) {
-      const uint64_t skip = do_reset ? ~0ull : L.sc->dist_hit;  // (and every agent with M < 0)
-      // dist_window overwrites dist_pre with the POST terms; without the
-      // prefetch every lane of the slot read all agents' PRE terms in the
-      // reward above, and in a multi-wave slot another wave may still be
-      // there: every wave passes the reward before any POST store
-      if constexpr (NT > 64 && !kPrePrefetch) __syncthreads();
-      if (MC_ABL != 1) {
-        // (tried, round 5: one lane per (agent, target row) growing the
-        // row's covered set by a bit-parallel dilation -- 83.6 against 81.7
-        // us at the C5 steady state, profiles/r5/win/; removed)
-        if constexpr (LPE % 32 == 0) {
-          if constexpr (SH::N > 0 && SH::N <= 64) {
-            if (5 + s.E * s.E <= 32) dist_window_am2(s, C, skip);
-            else dist_window(s, C, skip);
-          } else {
-            if (5 + s.E * s.E <= 32) dist_window_am(s, C, skip);
-            else dist_window(s, C, skip);
-          }
-        } else {
-          dist_window(s, C, skip);
-        }
-      }
-      __syncthreads();
-      dlist = C.sub < N && ((((skip | L.sc->dist_fail) >> C.sub) & 1ull) || L.dm[C.sub] < 0);
-    }
+    if (s.dist) dlist = dist_post(s, C, N, do_reset);
     // several waves: the slot's Scal reads above come before reset_env's
     // writes (one wave: its LDS operations complete in order)
     if constexpr (NT > 64) __syncthreads();
@@ -2823,7 +2981,7 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
       // prefetch gains), and a reset issues nothing
       if constexpr (kVisPre) {
         if (vis_more) {
-          const bool nblk = !ninb || ((tn >> tile_bit(ntx, nty)) & 1ull);
+          const bool nblk = target_blocked(Tn, tn);
           vis_prefetch(s, C, g0, I, xy_after, fuse_predict_cell(xy_next, act_next, nblk), nblk, VK);
         }
       }
@@ -2837,25 +2995,8 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
     reset_env(s, C, reset_req ? io.inj_pos : nullptr);
     dlist = s.dist && C.sub < N;  // fresh maps: M unknown
   } else {
-    // sentinel step without auto-reset / env left out of a partial reset:
-    // obs of the current state only (dec_grid_rl.py:104-107,160).  Only the
-    // old free / obstacle tiles are needed (fold / oold): no row or column
-    // plane is scattered.  With the fan march the column planes overlay
-    // fold / oold (carve), and a multi-wave slot's column-byte stores would
-    // race with another wave's stage_fold stores.
     reload_state<SH, EPW, LOOP>(s, io, k);
-    Items<KI> I;
-    stage_load(s, C, g0, true, I);
-    stage_fold(s, C, I);
-    // unchanged maps keep their dist terms; an unknown M (a state upload)
-    // needs the full transform
-    dlist = s.dist && C.sub < N && L.dm[C.sub] < 0;
-    if (C.sub == 0 && sentinel) sentinel_done(s, io, e, g0, free_old, currstep0);
-    // (CARRY: the grid tiles stage_load read for nothing land here, inside the
-    // arm.  It is laid out ahead of the active path, and a load it left in
-    // flight made that path's moves wait for all but its newest loads, the
-    // last step's stores among them)
-    if constexpr (CT::CARRY) __builtin_amdgcn_s_waitcnt(0x0F70);
+    dlist = obs_only(s, io, C, N, g0, sentinel, free_old, currstep0);
   }
   __syncthreads();
 
@@ -2866,54 +3007,8 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
   const bool p_active = kPathLds ? (path & kPathActive) != 0 : active;
   const bool p_reset_req = kPathLds ? (path & kPathResetReq) != 0 : reset_req;
   const bool p_sent_reset = kPathLds ? (path & kPathSentReset) != 0 : sent_reset;
-  if (p_active || p_reset_req || p_sent_reset) {
-    if (C.sub < N)
-      el<O32>(reinterpret_cast<int2*>(s.pos), (uint32_t)e * (uint32_t)N + C.sub) = make_int2(L.x[C.sub], L.y[C.sub]);
-    if (C.sub == 0) el<O32>(s.rec, e).moved = L.sc->moved;
-    // dist_reward: a reset map, or one whose witness got closer than M,
-    // has an unknown M now (recomputed by the full transform, mc_dist.hip)
-    if (s.dist && C.sub < N &&
-        (p_reset_req || p_sent_reset || L.sc->do_reset || ((L.sc->dist_hit >> C.sub) & 1ull)))
-      s.dist_mw[((size_t)e * N + C.sub) * 2] = -1;
-    if (s.dist_ch && C.sub < N) {
-      int* hp = s.dist_ch + ((size_t)e * N + C.sub) * 8;
-      if (p_reset_req || p_sent_reset || L.sc->do_reset) {
-        hp[0] = -1;  // the map was cleared: the cached cells' d are stale
-      } else if (chd.x > 0) {  // every newly covered cell lies in the sensing window
-        const int x = L.x[C.sub], y = L.y[C.sub], H = s.H;
-        *reinterpret_cast<int4*>(hp) = make_int4(chd.x, chd.y, min(chd.z, x - H), min(chd.w, y - H));
-        *reinterpret_cast<int2*>(hp + 4) = make_int2(max(chb.x, x + H), max(chb.y, y + H));
-      }
-    }
-  }
-  if (s.dist) {
-    // the full transform's work list (mc_dist.hip launch_dist_listed): one
-    // atomic per env slot of the wave on its env's shard (e % kListShards,
-    // spread over kListShards lines: early after a reset nearly every env
-    // appends, ~8k returning atomics per step on one address), the slot's
-    // entries at consecutive places of the shard
-    const bool me = valid && dlist;
-    const uint64_t m = __ballot(me);
-    if (m) {
-      const int lane = C.lane;
-      const uint64_t slotm = LPE >= 64 ? ~0ull : (low_mask(LPE) << (lane & ~(LPE - 1) & 63));
-      const uint64_t ms = m & slotm;
-      if (ms) {
-        const int leader = __ffsll((unsigned long long)ms) - 1;
-        const uint32_t sh = (uint32_t)e % (uint32_t)kListShards;
-        uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(s.dist_shc + sh * kShardStride, (uint32_t)__popcll(ms));
-        base = (uint32_t)__shfl((int)base, leader);
-        if (me)
-          s.dist_cnt[5 + sh * s.dist_cap + base + __popcll(ms & ((1ull << lane) - 1ull))] =
-              (uint32_t)e * (uint32_t)N + (uint32_t)C.sub;
-      }
-    }
-    if (s.dist_full && blockIdx.x == 0 && threadIdx.x == 0) {  // the last step's full list is done
-      s.dist_full[2] = s.dist_full[0];
-      s.dist_full[0] = 0;
-    }
-  }
+  if (p_active || p_reset_req || p_sent_reset) commit_state(s, C, N, p_reset_req || p_sent_reset, chd, chb);
+  if (s.dist) dist_list_append(s, C, N, valid && dlist);
   STAMP(8);
   reload_state<SH, EPW, LOOP>(s, io, k);
   if constexpr (CT::OBS_FAST) {
@@ -2922,15 +3017,8 @@ __device__ __forceinline__ void env_step(State& s, EnvIO& io, CT& C, const bool 
     if (valid) write_obs(s, C, io.obs_out);
   }
   STAMP(9);
-  if (io.adj_out != nullptr) {  // updateCommmunicationGraph (:374-391); the uniform test first
-    if (valid) {
-      uint8_t* ad = io.adj_out + (size_t)e * N * N;
-      for (int idx = C.sub; idx < N * N; idx += LPE) {
-        const int i = idx / N, j = idx - i * N;
-        const int dx = abs(L.x[i] - L.x[j]), dy = abs(L.y[i] - L.y[j]);
-        ad[idx] = (max(dx, dy) <= s.comm_r) ? 1 : 0;
-      }
-    }
+  if (io.adj_out != nullptr) {  // the uniform test first
+    if (valid) write_adj(s, C, N, io.adj_out);
   }
 #ifdef MC_STAMPS
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
