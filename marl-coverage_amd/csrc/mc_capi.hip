@@ -2,24 +2,25 @@
 // Owns the device state of a batch of envs and launches mc_kernels.hip.
 #include <hip/hip_runtime.h>
 
-#include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <memory>
 #include <string>
-#include <algorithm>
 #include <vector>
 
 #include "marlcov.h"
 #include "mc_internal.h"
+#include "mc_beams.h"
+#include "mc_config.h"
 #include "mc_env_select.h"
 #include "mc_export.h"
 #include "mc_fork.h"
 #include "mc_frontier.h"
 #include "mc_fuse.h"
+#include "mc_host.h"
 #include "mc_import.h"
 #include "mc_vistab.h"
 
@@ -65,31 +66,14 @@ __global__ void dijkstra_kernel(State s, int pad, int layer, int Lc, uint8_t* ob
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
-
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) return fail(MC_EHIP, "%s: %s", #expr, hipGetErrorString(_e)); \
-  } while (0)
+using mc::fail;
 
 struct Env {
   mc_config cfg;
   double range = 0.0;
   mc_layout lay;
   mc::State s;
-  int device = 0;
+  int device = -1;  // (-1: none yet, mc_create before its hipSetDevice)
   int nt = 128;
   int epw = 1;  // envs per workgroup (2: two envs share one wave)
   // steps per env-kernel launch of a fused mc_step_many call (MARLCOV_FUSE_STEPS,
@@ -118,17 +102,15 @@ struct Env {
   uint32_t* dist_full = nullptr;  // with the cache: the split transform's list (mc_dist.hip mode 2)
   bool dist_pre_stale = true;  // dist_pre does not describe the current maps
   bool beams_set = false;
-  void* beams_buf = nullptr;  // mc::Beam [beam_count]
-  void* bits_buf = nullptr;   // u64 [beam_count][max(Wp, Lp)]
-  void* fan_buf = nullptr;    // u32 [State::fan_words]: fan march data (dense beam sets)
-  size_t fan_cap = 0;         // words allocated in fan_buf
-  void* rayprog_buf = nullptr;  // u32: the ray programs (State::ray_prog; common beam patterns)
-  size_t rayprog_cap = 0;       // words allocated in rayprog_buf
+  mc::DevBuf beams;    // mc::Beam [beam_count]
+  mc::DevBuf bits;     // u64 [beam_count][max(Wp, Lp)]
+  mc::DevBuf fan;      // u32 [State::fan_words]: fan march data (dense beam sets)
+  mc::DevBuf rayprog;  // u32: the ray programs (State::ray_prog; common beam patterns)
   // the lidar's visibility table (State::vis_tab; mc_vistab.h): MARLCOV_VIS_TABLE
   // 0 off / 1 on (default) / 2 require, and MARLCOV_VIS_TABLE_MB, read at mc_create
   int vis_mode = 1;
   size_t vis_cap = 0;       // largest table to build, bytes
-  void* vis_buf = nullptr;  // G x Wp x Lp records (allocated at the first build)
+  mc::DevBuf vis;           // G x Wp x Lp records (allocated at the first build)
   int beam_count = 0;
   bool grids_set = false;
   std::vector<void*> allocs;
@@ -183,18 +165,17 @@ FieldDesc field(Env* E, int f) {
 #undef REC_FIELD
 }
 
-int dev_alloc(Env* E, void** p, size_t bytes) {
-  void* q = nullptr;
-  HIP_TRY(hipMalloc(&q, bytes < 16 ? 16 : bytes));
-  HIP_TRY(hipMemset(q, 0, bytes < 16 ? 16 : bytes));
-  E->allocs.push_back(q);
-  *p = q;
-  return MC_OK;
-}
-
 Env* as_env(void* p) { return static_cast<Env*>(p); }
 
-int launch_epw(const Env* E);
+// envs per workgroup for this launch; MARLCOV_EPW=1 forces one env per
+// workgroup (A/B tuning)
+int launch_epw(const Env* E) {
+  static const int force = [] {
+    const char* v = getenv("MARLCOV_EPW");
+    return v ? atoi(v) : 0;
+  }();
+  return force == 1 ? 1 : E->epw;
+}
 
 // (Re)build the visibility table on `st` after the pool or the beam table
 // changed -- once both are there -- or drop it when this state's step kernel
@@ -213,14 +194,13 @@ int vis_refresh(Env* E, hipStream_t st, const char* who) {
   else if (cells >= (1ull << 31) || bytes > E->vis_cap)
     snprintf(why, sizeof(why), "the pool's table of %llu MB exceeds MARLCOV_VIS_TABLE_MB = %llu",
              (unsigned long long)(bytes >> 20), (unsigned long long)(E->vis_cap >> 20));
-  else if (!E->vis_buf && hipMalloc(&E->vis_buf, (size_t)bytes) != hipSuccess) {
+  else if (!E->vis.p && E->vis.reserve((size_t)bytes) != hipSuccess) {
     (void)hipGetLastError();  // (cleared: the fallback is not an error)
-    E->vis_buf = nullptr;
     snprintf(why, sizeof(why), "allocating the table's %llu MB failed", (unsigned long long)(bytes >> 20));
   }
   if (why[0]) return E->vis_mode == 2 ? fail(MC_EINVAL, "%s: MARLCOV_VIS_TABLE=require, but %s", who, why) : MC_OK;
-  HIP_TRY(mc::launch_vis_build(s, (uint32_t*)E->vis_buf, st));
-  s.vis_tab = (const uint32_t*)E->vis_buf;
+  HIP_TRY(mc::launch_vis_build(s, (uint32_t*)E->vis.p, st));
+  s.vis_tab = (const uint32_t*)E->vis.p;
   return MC_OK;
 }
 
@@ -233,28 +213,113 @@ void set_launch_shape(Env* E) {
   E->epw = g.epw;
 }
 
-// envs per workgroup for this launch; MARLCOV_EPW=1 forces one env per
-// workgroup (A/B tuning)
-int launch_epw(const Env* E) {
-  static const int force = [] {
-    const char* v = getenv("MARLCOV_EPW");
-    return v ? atoi(v) : 0;
-  }();
-  return force == 1 ? 1 : E->epw;
+// mc_create's switches, per handle (not cached: tests set them per env): the
+// visibility table's and the fused launches'
+void read_switches(Env* E) {
+  if (const char* v = getenv("MARLCOV_VIS_TABLE")) E->vis_mode = v[0] == '0' ? 0 : (strcmp(v, "require") == 0 ? 2 : 1);
+  E->vis_cap = (size_t)16384 << 20;
+  if (const char* v = getenv("MARLCOV_VIS_TABLE_MB")) E->vis_cap = (size_t)strtoull(v, nullptr, 10) << 20;
+  E->fuse_steps = mc::fuse_steps_from_env(getenv("MARLCOV_FUSE_STEPS"));
+}
+
+// The BFS kernel of dijkstra_input or the frontier call (`who`): the bitboards
+// of one (env, agent) live in one workgroup's LDS where they fit (*lds: their
+// bytes); else (or with MARLCOV_DJ_BIG=1: tests of the HBM kernel at small
+// shapes) in an HBM scratch, a slot per workgroup of the HBM kernel (*lds = 0;
+// allocated here unless `scratch` names one already)
+int choose_bfs(Env* E, const char* who, size_t* lds, uint64_t*& scratch, unsigned& slots) {
+  const mc::State& s = E->s;
+  const mc_config& c = E->cfg;
+  *lds = mc::dijkstra_lds_bytes(s, c.pad);
+  int maxlds = 0;
+  if (hipDeviceGetAttribute(&maxlds, hipDeviceAttributeMaxSharedMemoryPerBlock, E->device) != hipSuccess)
+    return fail(MC_EHIP, "%s: cannot query the device's LDS per workgroup", who);
+  if (*lds + 1024 <= (size_t)maxlds && !mc::env_is_1("MARLCOV_DJ_BIG")) return MC_OK;
+  *lds = 0;
+  if (scratch) return MC_OK;
+  slots = mc::dijkstra_big_slots(s, c.pad);
+  const size_t bytes = (size_t)slots * mc::dijkstra_big_slot_bytes(s, c.pad);
+  if (mc::dev_alloc(E->allocs, scratch, bytes / 8) != MC_OK)
+    return fail(MC_EHIP, "%s: %zu B of scratch (%u slots) for a %dx%d grid: %s", who, bytes, slots, c.width, c.length,
+                mc::g_last_error.c_str());
+  E->lay.state_bytes += (int64_t)bytes;
+  return MC_OK;
+}
+
+const char* bfs_name(bool window, bool big) { return window ? (big ? "window+hbm" : "window+lds") : (big ? "hbm" : "lds"); }
+
+// mc_create with dijkstra_input: the BFS kernel's choice, its scratch and its item list
+int setup_dijkstra(Env* E) {
+  const mc::State& s = E->s;
+  const mc_config& c = E->cfg;
+  // the end point of a path is the int32 cell index u * RY + v of the extended grid
+  if (((int64_t)s.Wp + 2 * c.pad) * ((int64_t)s.Lp + 2 * c.pad) > INT32_MAX)
+    return fail(MC_EINVAL, "dijkstra_input: the %dx%d grid's extended cells exceed a 32-bit index", c.width, c.length);
+  if (int rc = choose_bfs(E, "dijkstra_input", &E->dj_lds, E->dj_big, E->dj_big_slots); rc != MC_OK) return rc;
+  if (mc::dev_alloc(E->allocs, E->dj_list, (size_t)s.B * s.N + 3) != MC_OK)
+    return fail(MC_EHIP, "dijkstra_input state: %s", mc::g_last_error.c_str());
+  E->dj_window = !mc::env_is_1("MARLCOV_DJ_FULL");  // parity tests: every item on the full map
+  return MC_OK;
+}
+
+// mc_create with dist_reward: the transform's limits, its terms and work
+// lists, and the top-cell cache where it applies
+int setup_dist(Env* E) {
+  mc::State& s = E->s;
+  const mc_config& c = E->cfg;
+  if (c.width + c.length + 4 * c.pad >= 65535)
+    return fail(MC_EINVAL, "dist_reward: grid %dx%d too large for 16-bit distances", c.width, c.length);
+  if (s.Wp + 2 * c.pad > mc::dist_max_rows())
+    return fail(MC_EINVAL, "dist_reward: %d extended rows exceed the transform's %d", s.Wp + 2 * c.pad,
+                mc::dist_max_rows());
+  if (s.Lp + 2 * c.pad > 32767)  // the witness column is a signed 16-bit half (mc_device.h)
+    return fail(MC_EINVAL, "dist_reward: %d extended columns exceed 32767", s.Lp + 2 * c.pad);
+  const size_t need = mc::dist_lds_bytes(s, c.pad);
+  int maxlds = 0;
+  if (hipDeviceGetAttribute(&maxlds, hipDeviceAttributeMaxSharedMemoryPerBlock, E->device) != hipSuccess ||
+      need + mc::dist_static_lds_bytes() + 1024 > (size_t)maxlds)
+    return fail(MC_EINVAL, "dist_reward: %zu B of LDS bitboards for a %dx%d grid exceed the "
+                "device's %d B per workgroup", need, c.width, c.length, maxlds);
+  E->dt_lds = need;
+  std::vector<void*>& A = E->allocs;
+  const size_t maps = (size_t)s.B * s.N;
+  if (int rc = mc::dev_alloc(A, E->dist_pre, maps * 8); rc != MC_OK) return rc;
+  s.dist_pre = E->dist_pre;
+  // (M, witness) per map, M = -1 (unknown) until a full transform; the
+  // work list of the full transform and its count
+  const size_t cap = (size_t)((s.B + mc::kListShards - 1) / mc::kListShards) * s.N;  // entries per shard
+  if (mc::dev_alloc(A, s.dist_mw, maps * 2, 0xFF) || mc::dev_alloc(A, E->dist_list, mc::kListShards * cap + 5) ||
+      mc::dev_alloc(A, s.dist_tot, 4) || mc::dev_alloc(A, s.dist_shc, (size_t)mc::kListShards * mc::kShardStride))
+    return fail(MC_EHIP, "dist_reward state: %s", mc::g_last_error.c_str());
+  s.dist_cnt = E->dist_list;
+  s.dist_cap = (uint32_t)cap;
+  // the top-cell cache (mc_dist.hip), off with map sharing (other agents'
+  // maps add cells outside the agent's own sensing windows) or
+  // MARLCOV_DIST_CACHE=0, and off for maps past the LDS-bitboard transform's
+  // rows (the big-map kernel transforms every listed map whole, mc_dist.hip)
+  if (c.map_sharing || mc::env_starts_0("MARLCOV_DIST_CACHE") || s.Wp + 2 * c.pad > mc::dist_cache_max_rows())
+    return MC_OK;
+  const size_t gparts = (size_t)mc::kDistGSlots * mc::kDistGParts;
+  uint32_t* full = nullptr;
+  if (mc::dev_alloc(A, s.dist_cc, maps * mc::kDistK) || mc::dev_alloc(A, s.dist_cd, maps * mc::kDistK) ||
+      mc::dev_alloc(A, s.dist_ch, maps * 8, 0xFF) || mc::dev_alloc(A, s.dist_sm, maps * mc::kDistStrips) ||
+      mc::dev_alloc(A, s.dist_gkey, maps) || mc::dev_alloc(A, s.dist_gcnt, gparts) ||
+      mc::dev_alloc(A, s.dist_pcnt, maps) || mc::dev_alloc(A, s.dist_govf, (size_t)mc::kDistGSlots) ||
+      mc::dev_alloc(A, s.dist_rmask, maps) || mc::dev_alloc(A, s.dist_gcand, gparts * mc::kDistK) ||
+      mc::dev_alloc(A, full, maps * 2 + 8))
+    return fail(MC_EHIP, "dist_reward cache: %s", mc::g_last_error.c_str());
+  // MARLCOV_DIST_SPLIT=0: every listed map's full transform in one workgroup
+  if (!mc::env_starts_0("MARLCOV_DIST_SPLIT")) E->dist_full = s.dist_full = full;
+  return MC_OK;
 }
 
 }  // namespace
-
-namespace mc {
-// shared with mc_super.hip: one thread-local message for mc_last_error()
-void set_last_error(const char* msg) { g_err = msg; }
-}  // namespace mc
 
 extern "C" {
 
 int32_t mc_abi_version(void) { return MARLCOV_ABI_VERSION; }
 
-const char* mc_last_error(void) { return g_err.c_str(); }
+const char* mc_last_error(void) { return mc::g_last_error.c_str(); }
 
 int64_t mc_struct_size(int32_t which) {
   switch (which) {
@@ -279,295 +344,43 @@ int mc_create(const mc_config* cfg, int hip_device, void** out_env) {
   if (!cfg || !out_env) return fail(MC_EINVAL, "mc_create: null argument");
   *out_env = nullptr;
   const mc_config& c = *cfg;
-  if (c.num_envs < 1) return fail(MC_EINVAL, "num_envs must be >= 1 (got %d)", c.num_envs);
-  if (c.num_agents < 1 || c.num_agents > 64)
-    return fail(MC_EINVAL, "numrobot must be in [1, 64] (got %d)", c.num_agents);
-  if (c.width < 3 || c.length < 3 || c.width > 32767 || c.length > 32767)
-    return fail(MC_EINVAL, "padded grid %dx%d out of range", c.width, c.length);
-  if (c.num_grids < 1) return fail(MC_EINVAL, "num_grids must be >= 1");
-  if (c.sensor_type != MC_SENSOR_LIDAR && c.sensor_type != MC_SENSOR_SQUARE)
-    return fail(MC_EINVAL, "unknown sensor_type %d", c.sensor_type);
-  if (c.sensor_type == MC_SENSOR_LIDAR && c.num_beams < 1)
-    return fail(MC_EINVAL, "num_lasers must be >= 1");
-  if (c.sensor_type == MC_SENSOR_SQUARE && c.square_radius < 0)
-    return fail(MC_EINVAL, "square sensor range must be >= 0");
-  if (c.egoradius < 0) return fail(MC_EINVAL, "egoradius must be >= 0");
-  if (c.pad < c.egoradius) return fail(MC_EINVAL, "pad must be >= egoradius");
-  if (c.mini_map_rad < 0 || c.pad < c.mini_map_rad) return fail(MC_EINVAL, "need 0 <= mini_map_rad <= pad");
-  if (c.mini_map_rad > 0 && 2 * c.egoradius + 1 > 32)
-    return fail(MC_EINVAL, "minimap layers need egoradius <= 15");
-  if (!(c.lidar_range == c.lidar_range)) return fail(MC_EINVAL, "lidar range is NaN");
-  if (c.maxsteps < 0) return fail(MC_EINVAL, "maxsteps must be >= 0");
-
-  int hs = 0;
-  if (c.sensor_type == MC_SENSOR_LIDAR) {
-    // every marked cell is within Chebyshev ceil(range) of the robot: the
-    // major axis moves exactly 1 per step and the fp64 distance sum of
-    // increments >= 1 reaches range after at most ceil(range) steps
-    hs = c.lidar_range > 0 ? (int)ceil(c.lidar_range) : 0;
-    if (c.lidar_range > 31) return fail(MC_EINVAL, "lidar range %g > 31 not supported", c.lidar_range);
-  } else {
-    hs = c.square_radius;
-  }
-  const int H = hs > c.egoradius ? hs : c.egoradius;
-  const int TW = mc::window_tiles(H);
-  if (2 * c.egoradius + 1 > 32)
-    return fail(MC_EINVAL, "egoradius %d > 15: obs crop rows are 32-bit", c.egoradius);
-  if ((int64_t)c.num_agents * TW * TW > (int64_t)mc::kMaxItemsPerLane * 1024)
-    return fail(MC_EINVAL, "numrobot * %d^2 window tiles = %d exceeds %d (range/egoradius too large)",
-                TW, c.num_agents * TW * TW, mc::kMaxItemsPerLane * 1024);
-  {
-    // the kernels index maps with 32-bit words and 24-bit factors
-    const int64_t tiles = (int64_t)(((c.width + 7) / 8 + 3) / 4) * (((c.length + 7) / 8 + 3) / 4) * 16;
-    if ((int64_t)c.num_envs * c.num_agents * tiles >= ((int64_t)1 << 32) ||
-        (int64_t)c.num_envs * c.num_agents >= ((int64_t)1 << 24) || tiles >= ((int64_t)1 << 24))
-      return fail(MC_EINVAL, "num_envs * numrobot * map tiles = %lld exceeds 2^32 words per handle",
-                  (long long)c.num_envs * c.num_agents * tiles);
-  }
-  if (TW > mc::kMaxWindowTiles)
-    return fail(MC_EINVAL, "window half-width H = %d > 27 (range/egoradius too large)", H);
-  if (mc::env_lds_bytes(c.num_agents, TW, c.sensor_type == MC_SENSOR_LIDAR ? c.num_beams : 0,
-                        TW <= 4 ? 4 : 8) > 65536)
-    return fail(MC_EINVAL, "per-env LDS window exceeds 64 KiB (numrobot / range / num_lasers too large)");
-
-  // the visibility table's switches, per handle (not cached: tests set them per env)
-  int vis_mode = 1;
-  size_t vis_cap = (size_t)16384 << 20;
-  if (const char* v = getenv("MARLCOV_VIS_TABLE")) vis_mode = v[0] == '0' ? 0 : (strcmp(v, "require") == 0 ? 2 : 1);
-  if (const char* v = getenv("MARLCOV_VIS_TABLE_MB")) vis_cap = (size_t)strtoull(v, nullptr, 10) << 20;
-  if (vis_mode == 2 && (c.sensor_type != MC_SENSOR_LIDAR || !mc::vis_fits(H)))
+  std::string err;
+  if (!mc::check_config(c, err)) return fail(MC_EINVAL, "%s", err.c_str());
+  std::unique_ptr<Env, mc::HandleDeleter<mc_destroy>> E(new Env());
+  E->cfg = c;
+  read_switches(E.get());
+  const int H = mc::window_half(c);
+  if (E->vis_mode == 2 && (c.sensor_type != MC_SENSOR_LIDAR || !mc::vis_fits(H)))
     return fail(MC_EINVAL, "mc_create: MARLCOV_VIS_TABLE=require, but a visibility record holds a lidar of "
                 "half-width <= %d only (this env: %s, H = %d)", (mc::kVisRows - 1) / 2,
                 c.sensor_type == MC_SENSOR_LIDAR ? "lidar" : "square sensor", H);
-
-  Env* E = new Env();
-  E->cfg = c;
-  E->vis_mode = vis_mode;
-  E->vis_cap = vis_cap;
-  E->fuse_steps = mc::fuse_steps_from_env(getenv("MARLCOV_FUSE_STEPS"));
   E->range = c.lidar_range;
-  E->device = hip_device;
   mc::State& s = E->s;
-  s.B = c.num_envs;
-  s.N = c.num_agents;
-  s.Wp = c.width;
-  s.Lp = c.length;
-  s.TR = (c.width + 7) / 8;
-  s.TC = (c.length + 7) / 8;
-  s.TRS = (s.TR + 3) / 4;
-  s.TCS = (s.TC + 3) / 4;
-  s.MT = s.TRS * s.TCS * 16;
-  s.G = c.num_grids;
-  s.H = H;
-  s.TW = TW;
-  s.mg_TW = mc::magic_div((uint32_t)TW);
-  s.mg_TW2 = mc::magic_div((uint32_t)(TW * TW));
-  s.ego = c.egoradius;
-  s.pad = c.pad;
-  s.E = 2 * c.egoradius + 1;
-  s.Lc = (c.mini_map_rad > 0 ? 5 : 3) + (c.dist_reward ? 1 : 0) + (c.dijkstra_input ? 1 : 0);
-  s.dist = c.dist_reward ? 1 : 0;
-  s.mg_LcE = mc::magic_div((uint32_t)(s.Lc * s.E));
-  s.mg_E = mc::magic_div((uint32_t)s.E);
-  s.sensor = c.sensor_type;
-  s.nbeams = c.sensor_type == MC_SENSOR_LIDAR ? c.num_beams : 0;
-  s.mg_nb = mc::magic_div((uint32_t)(s.nbeams > 0 ? s.nbeams : 1));
-  s.sq_r = c.square_radius;
-  s.pen = c.collision_penalty;
-  s.term = c.terminal_reward;
-  s.dincr = c.done_incr;
-  s.maxsteps = c.maxsteps;
-  s.comm_r = c.comm_radius;
-  s.sst = c.single_square_tool ? 1 : 0;
-  s.auto_reset = c.auto_reset ? 1 : 0;
-  s.grid_mode = c.reset_grid_mode;
-  s.seed = c.seed;
-  s.env0 = c.env_offset;
-  s.grid0 = c.grid_offset;
-
-  hipError_t he = hipSetDevice(hip_device);
-  if (he != hipSuccess) {
-    delete E;
+  mc::derive_state(c, s);
+  if (const hipError_t he = hipSetDevice(hip_device); he != hipSuccess)
     return fail(MC_EHIP, "hipSetDevice(%d): %s", hip_device, hipGetErrorString(he));
-  }
+  E->device = hip_device;
   const size_t B = s.B, N = s.N, mw = (size_t)s.MT, G = s.G;
-  void* p = nullptr;
-  int rc = MC_OK;
   size_t total = 0;
-#define ALLOC(dst, T, count)                                  \
-  do {                                                        \
-    if (rc == MC_OK) rc = dev_alloc(E, &p, (count) * sizeof(T)); \
-    dst = (T*)p;                                              \
-    total += (count) * sizeof(T);                             \
-  } while (0)
-  uint64_t *gneg = nullptr, *gpos = nullptr;
-  int32_t* nfree = nullptr;
-  ALLOC(gneg, uint64_t, G * mw);
-  ALLOC(gpos, uint64_t, G * mw);
-  ALLOC(nfree, int32_t, G);
-  ALLOC(s.rec, mc::EnvRec, B);
-  ALLOC(s.pos, int32_t, B * N * 2);
+  int rc = MC_OK;
+  auto alloc = [&](auto*& dst, size_t count) {
+    total += count * sizeof(*dst);
+    return rc = mc::dev_alloc(E->allocs, dst, count);
+  };
   // one extra tile past each mask array stays zero: the env kernel's staged
   // tiles outside the map read it (no select on the loaded value)
-  ALLOC(s.freem, uint64_t, B * N * mw + 1);
-  ALLOC(s.obstm, uint64_t, B * N * mw + 1);
-  ALLOC(s.vis, uint64_t, B * mw + 1);
-  ALLOC(s.err, uint32_t, 4);
-  ALLOC(s.ep_pc, double, B);
-  ALLOC(s.ep_len, int32_t, B);
-#undef ALLOC
-  s.grid_neg = gneg;
-  s.grid_pos = gpos;
-  s.numfree = nfree;
-  if (rc != MC_OK) {
-    std::string msg = g_err;
-    mc_destroy(E);
-    return fail(rc, "%s", msg.c_str());
+  if (alloc(s.grid_neg, G * mw) || alloc(s.grid_pos, G * mw) || alloc(s.numfree, G) || alloc(s.rec, B) ||
+      alloc(s.pos, B * N * 2) || alloc(s.freem, B * N * mw + 1) || alloc(s.obstm, B * N * mw + 1) ||
+      alloc(s.vis, B * mw + 1) || alloc(s.err, 4) || alloc(s.ep_pc, B) || alloc(s.ep_len, B))
+    return rc;
+  std::vector<mc::EnvRec> recs(B);  // (value-initialised: zero)
+  for (size_t i = 0; i < B; ++i) {
+    recs[i].env_grid = (int32_t)(i % G);
+    recs[i].done_thresh = c.done_thresh;
   }
-  {
-    std::vector<mc::EnvRec> recs(B);  // (value-initialised: zero)
-    for (size_t i = 0; i < B; ++i) {
-      recs[i].env_grid = (int32_t)(i % G);
-      recs[i].done_thresh = c.done_thresh;
-    }
-    if (hipMemcpy(s.rec, recs.data(), B * sizeof(mc::EnvRec), hipMemcpyHostToDevice) != hipSuccess) {
-      mc_destroy(E);
-      return fail(MC_EHIP, "mc_create: initial upload failed");
-    }
-  }
-  set_launch_shape(E);
-  if (c.dijkstra_input) {
-    // the end point of a path is the int32 cell index u * RY + v of the extended grid
-    if (((int64_t)s.Wp + 2 * c.pad) * ((int64_t)s.Lp + 2 * c.pad) > INT32_MAX) {
-      mc_destroy(E);
-      return fail(MC_EINVAL, "dijkstra_input: the %dx%d grid's extended cells exceed a 32-bit index",
-                  c.width, c.length);
-    }
-    // the BFS bitboards of one (env, agent) live in one workgroup's LDS where
-    // they fit; else (or with MARLCOV_DJ_BIG=1: tests of the HBM kernel at
-    // small shapes) in an HBM scratch, a slot per workgroup of the HBM kernel
-    const size_t need = mc::dijkstra_lds_bytes(s, c.pad);
-    int maxlds = 0;
-    if (hipDeviceGetAttribute(&maxlds, hipDeviceAttributeMaxSharedMemoryPerBlock, hip_device) !=
-        hipSuccess) {
-      mc_destroy(E);
-      return fail(MC_EHIP, "dijkstra_input: cannot query the device's LDS per workgroup");
-    }
-    const char* fb = getenv("MARLCOV_DJ_BIG");
-    if (need + 1024 > (size_t)maxlds || (fb && atoi(fb) == 1)) {
-      const unsigned slots = mc::dijkstra_big_slots(s, c.pad);
-      const size_t bytes = (size_t)slots * mc::dijkstra_big_slot_bytes(s, c.pad);
-      void* bq = nullptr;
-      if (dev_alloc(E, &bq, bytes) != MC_OK) {
-        std::string msg = g_err;
-        mc_destroy(E);
-        return fail(MC_EHIP, "dijkstra_input: %zu B of scratch (%u slots) for a %dx%d grid: %s", bytes,
-                    slots, c.width, c.length, msg.c_str());
-      }
-      E->dj_big = (uint64_t*)bq;
-      E->dj_big_slots = slots;
-      total += bytes;
-    } else {
-      E->dj_lds = need;
-    }
-    void* lq = nullptr;
-    if (dev_alloc(E, &lq, ((size_t)s.B * s.N + 3) * 4) != MC_OK) {
-      std::string msg = g_err;
-      mc_destroy(E);
-      return fail(MC_EHIP, "dijkstra_input state: %s", msg.c_str());
-    }
-    E->dj_list = (uint32_t*)lq;
-    const char* fo = getenv("MARLCOV_DJ_FULL");  // parity tests: every item on the full map
-    E->dj_window = !(fo && atoi(fo) == 1);
-  }
-  if (c.dist_reward) {
-    if (c.width + c.length + 4 * c.pad >= 65535) {
-      mc_destroy(E);
-      return fail(MC_EINVAL, "dist_reward: grid %dx%d too large for 16-bit distances", c.width,
-                  c.length);
-    }
-    if (s.Wp + 2 * c.pad > mc::dist_max_rows()) {
-      mc_destroy(E);
-      return fail(MC_EINVAL, "dist_reward: %d extended rows exceed the transform's %d", s.Wp + 2 * c.pad,
-                  mc::dist_max_rows());
-    }
-    if (s.Lp + 2 * c.pad > 32767) {  // the witness column is a signed 16-bit half (mc_device.h)
-      mc_destroy(E);
-      return fail(MC_EINVAL, "dist_reward: %d extended columns exceed 32767", s.Lp + 2 * c.pad);
-    }
-    const size_t need = mc::dist_lds_bytes(s, c.pad);
-    int maxlds = 0;
-    if (hipDeviceGetAttribute(&maxlds, hipDeviceAttributeMaxSharedMemoryPerBlock, hip_device) !=
-            hipSuccess ||
-        need + mc::dist_static_lds_bytes() + 1024 > (size_t)maxlds) {
-      mc_destroy(E);
-      return fail(MC_EINVAL, "dist_reward: %zu B of LDS bitboards for a %dx%d grid exceed the "
-                  "device's %d B per workgroup", need, c.width, c.length, maxlds);
-    }
-    E->dt_lds = need;
-    void* q = nullptr;
-    if (dev_alloc(E, &q, (size_t)s.B * s.N * 8 * sizeof(float)) != MC_OK) {
-      std::string msg = g_err;
-      mc_destroy(E);
-      return fail(MC_EHIP, "%s", msg.c_str());
-    }
-    E->dist_pre = (float*)q;
-    E->s.dist_pre = E->dist_pre;
-    // (M, witness) per map, M = -1 (unknown) until a full transform; the
-    // work list of the full transform and its count
-    void *mw = nullptr, *lq = nullptr, *tq = nullptr, *sh = nullptr;
-    const size_t cap = (size_t)((s.B + mc::kListShards - 1) / mc::kListShards) * s.N;  // entries per shard
-    if (dev_alloc(E, &mw, (size_t)s.B * s.N * 8) != MC_OK ||
-        dev_alloc(E, &lq, (mc::kListShards * cap + 5) * 4) != MC_OK || dev_alloc(E, &tq, 32) != MC_OK ||
-        dev_alloc(E, &sh, mc::kListShards * mc::kShardStride * 4) != MC_OK ||
-        hipMemset(mw, 0xFF, (size_t)s.B * s.N * 8) != hipSuccess) {
-      std::string msg = g_err;
-      mc_destroy(E);
-      return fail(MC_EHIP, "dist_reward state: %s", msg.c_str());
-    }
-    E->s.dist_mw = (int32_t*)mw;
-    E->dist_list = (uint32_t*)lq;
-    E->s.dist_cnt = E->dist_list;
-    E->s.dist_shc = (uint32_t*)sh;
-    E->s.dist_cap = (uint32_t)cap;
-    E->s.dist_tot = (unsigned long long*)tq;
-    // the top-cell cache (mc_dist.hip), off with map sharing (other agents'
-    // maps add cells outside the agent's own sensing windows) or
-    // MARLCOV_DIST_CACHE=0
-    const char* dc = getenv("MARLCOV_DIST_CACHE");
-    // and off for maps past the LDS-bitboard transform's rows (the big-map
-    // kernel transforms every listed map whole, mc_dist.hip)
-    if (!c.map_sharing && !(dc && dc[0] == '0') && s.Wp + 2 * c.pad <= mc::dist_cache_max_rows()) {
-      void *cc = nullptr, *cd = nullptr, *ch = nullptr, *sm = nullptr;
-      void *gk = nullptr, *gc = nullptr, *ga = nullptr, *fl = nullptr, *pc = nullptr, *rm = nullptr, *go = nullptr;
-      const size_t maps = (size_t)s.B * s.N;
-      if (dev_alloc(E, &cc, maps * mc::kDistK * 4) != MC_OK || dev_alloc(E, &cd, maps * mc::kDistK * 4) != MC_OK ||
-          dev_alloc(E, &ch, maps * 32) != MC_OK || hipMemset(ch, 0xFF, maps * 32) != hipSuccess ||
-          dev_alloc(E, &sm, maps * mc::kDistStrips * 4) != MC_OK || dev_alloc(E, &gk, maps * 8) != MC_OK ||
-          dev_alloc(E, &gc, (size_t)mc::kDistGSlots * mc::kDistGParts * 4) != MC_OK || dev_alloc(E, &pc, maps * 4) != MC_OK ||
-          dev_alloc(E, &go, (size_t)mc::kDistGSlots * 4) != MC_OK ||
-          dev_alloc(E, &rm, maps * 8) != MC_OK ||
-          dev_alloc(E, &ga, (size_t)mc::kDistGSlots * mc::kDistGParts * mc::kDistK * 8) != MC_OK ||
-          dev_alloc(E, &fl, (maps * 2 + 8) * 4) != MC_OK) {
-        std::string msg = g_err;
-        mc_destroy(E);
-        return fail(MC_EHIP, "dist_reward cache: %s", msg.c_str());
-      }
-      E->s.dist_cc = (int32_t*)cc;
-      E->s.dist_cd = (int32_t*)cd;
-      E->s.dist_ch = (int32_t*)ch;
-      E->s.dist_sm = (uint32_t*)sm;
-      E->s.dist_pcnt = (uint32_t*)pc;
-      E->s.dist_rmask = (unsigned long long*)rm;
-      E->s.dist_gkey = (unsigned long long*)gk;
-      E->s.dist_gcnt = (uint32_t*)gc;
-      E->s.dist_govf = (uint32_t*)go;
-      E->s.dist_gcand = (int2*)ga;
-      // MARLCOV_DIST_SPLIT=0: every listed map's full transform in one workgroup
-      const char* sp = getenv("MARLCOV_DIST_SPLIT");
-      if (!(sp && sp[0] == '0')) E->dist_full = E->s.dist_full = (uint32_t*)fl;
-    }
-  }
+  if (hipMemcpy(s.rec, recs.data(), B * sizeof(mc::EnvRec), hipMemcpyHostToDevice) != hipSuccess)
+    return fail(MC_EHIP, "mc_create: initial upload failed");
+  set_launch_shape(E.get());
   mc_layout& L = E->lay;
   L.tile_rows = 4 * s.TRS;
   L.tile_cols = 4 * s.TCS;
@@ -577,23 +390,21 @@ int mc_create(const mc_config* cfg, int hip_device, void** out_env) {
   L.obs_side = s.E;
   L.obs_bytes_per_env = (int64_t)N * s.Lc * s.E * s.E;
   L.mask_words_per_agent = (int64_t)mw;
+  // (the base arrays, and setup_dijkstra adds its HBM scratch; not the dist_reward arrays)
   L.state_bytes = (int64_t)total;
+  if (c.dijkstra_input && (rc = setup_dijkstra(E.get())) != MC_OK) return rc;
+  if (c.dist_reward && (rc = setup_dist(E.get())) != MC_OK) return rc;
   if (s.sensor != MC_SENSOR_LIDAR) E->beams_set = true;
-  *out_env = E;
+  *out_env = E.release();
   return MC_OK;
 }
 
 void mc_destroy(void* env) {
   Env* E = as_env(env);
   if (!E) return;
-  (void)hipSetDevice(E->device);
+  if (E->device >= 0) (void)hipSetDevice(E->device);
   for (void* p : E->allocs) (void)hipFree(p);
-  if (E->beams_buf) (void)hipFree(E->beams_buf);
-  if (E->bits_buf) (void)hipFree(E->bits_buf);
-  if (E->fan_buf) (void)hipFree(E->fan_buf);
-  if (E->rayprog_buf) (void)hipFree(E->rayprog_buf);
-  if (E->vis_buf) (void)hipFree(E->vis_buf);
-  delete E;
+  delete E;  // (and its DevBufs)
 }
 
 int mc_query(void* env, mc_layout* out) {
@@ -602,237 +413,28 @@ int mc_query(void* env, mc_layout* out) {
   return MC_OK;
 }
 
-// Fan march data of a dense beam set (mc_env_step.h fan_march, layout in
-// mc_internal.h State::fan_data).  Beams are grouped by octant class (major
-// axis, major sign, minor sign; minor sign 0 counts as +), ordered by their
-// minor offsets, and cut greedily into sectors of up to kFanS beams whose
-// offsets differ by 0 or 1 between neighbours at every step, at most one
-// start-dependent beam (Beam::axis bit 1) per sector.  The two classes of a
-// line (same major axis and sign, minor sign + / -) are paired: sector i of
-// each, interleaved step by step in one pair record (an empty sector pads the
-// shorter class), so one lane reads the line word once for both and marks it
-// with one OR; the pairs of the four lines are interleaved, so the pairs of
-// one march instruction mark different lines.
-// A start-dependent beam marches with its common bits except from the minor
-// starts where its own bits differ before the march ends (bits[b][start],
-// cm starts); the kernel marches those alone.  Returns false (ray march) for
-// sparse sets: fewer than 64 beams (dense_beams), or fewer than two beams per
-// sector on average.
-static bool build_fan(const std::vector<mc::Beam>& bt, const std::vector<uint64_t>& bits, int cmax, int Wp,
-                      int Lp, int kmax, int N, int lanes, std::vector<uint32_t>& out, int& nsec, int& nspec) {
-  const int nb = (int)bt.size();
-  if (nb < 64 || kmax > 27) return false;
-  auto off = [](const mc::Beam& o, int k) {  // signed minor offset of step k
-    return o.msign * __builtin_popcount(o.bits & ((1u << k) - 1u));
-  };
-  std::vector<std::vector<int>> cls(8);
-  std::vector<int> spec;
-  for (int b = 0; b < nb; ++b) {
-    const mc::Beam& o = bt[b];
-    if (o.axis & 2) spec.push_back(b);
-    cls[(o.axis & 1) * 4 + (o.sign < 0 ? 2 : 0) + (o.msign < 0 ? 1 : 0)].push_back(b);
-  }
-  std::vector<std::vector<std::vector<int>>> secs(8);
-  size_t most = 0;
-  for (int c = 0; c < 8; ++c) {
-    std::vector<int>& v = cls[c];
-    std::sort(v.begin(), v.end(), [&](int p, int q) {
-      for (int k = kmax; k >= 1; --k) {
-        const int a = off(bt[p], k), d = off(bt[q], k);
-        if (a != d) return a < d;
-      }
-      return p < q;
-    });
-    for (int b : v) {
-      std::vector<std::vector<int>>& S = secs[c];
-      bool join = !S.empty() && (int)S.back().size() < mc::kFanS;
-      if (join && (bt[b].axis & 2))
-        for (int o : S.back()) join = join && !(bt[o].axis & 2);
-      for (int k = 1; join && k <= kmax; ++k) {
-        const int d = off(bt[b], k) - off(bt[S.back().back()], k);
-        join = d == 0 || d == 1;
-      }
-      if (join) S.back().push_back(b);
-      else S.push_back({b});
-    }
-    most = std::max(most, secs[c].size());
-  }
-  static const std::vector<int> kNone;
-  std::vector<std::pair<const std::vector<int>*, const std::vector<int>*>> order;  // (minor +, minor -)
-  int real = 0;
-  for (size_t i = 0; i < most; ++i)
-    for (int m = 0; m < 4; ++m) {
-      const bool p = i < secs[2 * m].size(), q = i < secs[2 * m + 1].size();
-      if (p || q) order.push_back({p ? &secs[2 * m][i] : &kNone, q ? &secs[2 * m + 1][i] : &kNone});
-      real += (int)p + (int)q;
-    }
-  nsec = 2 * (int)order.size();  // sector slots (pairs x 2, empty ones included)
-  nspec = (int)spec.size();
-  if (2 * real > nb || N * nspec > lanes || nspec > 255) return false;
-  out.assign(mc::kFanLutBytes / 4, 0u);
-  uint8_t* lut = reinterpret_cast<uint8_t*>(out.data());
-  for (int D = 0; D < 32; ++D) {
-    int r[mc::kFanS] = {0};  // cell of beam i
-    for (int i = 1; i < mc::kFanS; ++i) r[i] = r[i - 1] + ((D >> (i - 1)) & 1);
-    for (int A = 0; A < 64; ++A) {
-      int lit = 0, kill = 0;
-      for (int i = 0; i < mc::kFanS; ++i) {
-        if ((A >> i) & 1) lit |= 1 << r[i];      // spread: beams A -> their cells
-        if ((A >> r[i]) & 1) kill |= 1 << i;     // expand: cells A -> the beams on them
-      }
-      lut[D * 64 + A] = (uint8_t)lit;
-      lut[2048 + D * 64 + A] = (uint8_t)kill;
-    }
-  }
-  auto cbits = [](const mc::Beam& o) {
-    return ((o.axis & 1) ? (uint32_t)mc::FAN_COLS : 0u) | (o.sign < 0 ? (uint32_t)mc::FAN_NEG : 0u);
-  };
-  // word 0 of a sector: its class bits and special beam; word k: step k's
-  // entry (an empty sector: the partner's class bits, entries 0 = no beam)
-  auto desc = [&](const std::vector<int>& v, uint32_t cls) {
-    uint32_t w0 = v.empty() ? cls : cbits(bt[v[0]]);
-    for (size_t j = 0; j < v.size(); ++j)
-      if (bt[v[j]].axis & 2) {
-        const size_t si = std::find(spec.begin(), spec.end(), v[j]) - spec.begin();
-        w0 |= mc::FAN_SPECIAL | ((uint32_t)j << 3) | ((uint32_t)si << 8);
-      }
-    return w0;
-  };
-  auto entry = [&](const std::vector<int>& v, int k) {
-    if (v.empty()) return 0u;
-    const int lo = off(bt[v[0]], k);
-    uint32_t D = 0, valid = 0;
-    for (size_t j = 0; j < v.size(); ++j) {
-      if (j + 1 < v.size() && off(bt[v[j + 1]], k) != off(bt[v[j]], k)) D |= 1u << j;
-      if (bt[v[j]].K >= k) valid |= 1u << j;
-    }
-    return (uint32_t)(lo + 32) | (D << 6) | (valid << 16);
-  };
-  for (const auto& pr : order) {  // pair record: [desc+, desc-], then [entry+(k), entry-(k)] per step
-    const std::vector<int>& v0 = *pr.first;
-    const std::vector<int>& v1 = *pr.second;
-    const uint32_t cls = cbits(bt[(v0.empty() ? v1 : v0)[0]]);
-    out.push_back(desc(v0, cls));
-    out.push_back(desc(v1, cls));
-    for (int k = 1; k <= kmax; ++k) {
-      out.push_back(entry(v0, k));
-      out.push_back(entry(v1, k));
-    }
-  }
-  for (int b : spec) {
-    // the starts whose own bits leave the common path before the march ends
-    // (the check of mc_set_beam_table's common-pattern test)
-    const mc::Beam& o = bt[b];
-    const int cm = (o.axis & 1) == 0 ? Lp : Wp;
-    const uint64_t* row = &bits[(size_t)b * cmax];
-    int elo = 1 << 30, ehi = -1;
-    for (int c0 = 1; c0 + 1 < cm; ++c0) {
-      int p = c0, c = c0;
-      for (int k = 0; k < o.K; ++k) {
-        p += ((row[c0] >> k) & 1) ? o.msign : 0;
-        c += ((o.bits >> k) & 1) ? o.msign : 0;
-        if (p != c) { elo = std::min(elo, c0); ehi = std::max(ehi, c0); break; }
-        if (p <= 0 || p >= cm - 1) break;
-      }
-    }
-    const uint32_t rec[8] = {(uint32_t)b, cbits(o), (uint32_t)o.msign, (uint32_t)o.K,
-                             (uint32_t)elo, (uint32_t)ehi, 0u, 0u};
-    out.insert(out.end(), rec, rec + 8);
-  }
-  while (out.size() % 4) out.push_back(0u);
-  return true;
+// u32 words into a buffer the handle grows as needed
+static int upload_words(mc::DevBuf& buf, const std::vector<uint32_t>& w) {
+  HIP_TRY(buf.reserve(w.size() * 4));
+  HIP_TRY(hipMemcpy(buf.p, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+  return MC_OK;
 }
 
 int mc_set_beam_table(void* env, const double* host_table, int32_t num_beams) {
   Env* E = as_env(env);
   if (!E || !host_table) return fail(MC_EINVAL, "mc_set_beam_table: null argument");
-  if (E->s.sensor != MC_SENSOR_LIDAR) return fail(MC_EINVAL, "beam table on a non-lidar env");
+  mc::State& s = E->s;
+  if (s.sensor != MC_SENSOR_LIDAR) return fail(MC_EINVAL, "beam table on a non-lidar env");
   if (num_beams < 1) return fail(MC_EINVAL, "beam table needs >= 1 beam");
   // the per-env LDS budget mc_create checked holds 16 B per beam: a new beam
   // count must fit it too, or the next launch would fail inside HIP
-  if (mc::env_lds_bytes(E->s.N, E->s.TW, num_beams, E->s.TW <= 4 ? 4 : 8) > 65536)
+  const int rb = s.TW <= 4 ? 4 : 8;
+  if (mc::env_lds_bytes(s.N, s.TW, num_beams, rb) > 65536)
     return fail(MC_EINVAL, "mc_set_beam_table: %d beams exceed the 64 KiB per-env LDS window", num_beams);
-  const int cmax = E->s.Wp > E->s.Lp ? E->s.Wp : E->s.Lp;
-  std::vector<mc::Beam> bt(num_beams);
-  std::vector<uint64_t> bits((size_t)num_beams * cmax, 0);
-  int kmax = 0, kmin = 1 << 30;
-  bool common = true;
-  for (int b = 0; b < num_beams; ++b) {
-    const double xi = host_table[3 * b], yi = host_table[3 * b + 1], di = host_table[3 * b + 2];
-    mc::Beam& o = bt[b];
-    double minor;
-    // lidar.py:43-45 normalises by max(|xinc|, |yinc|): one of them is +-1
-    if (fabs(xi) == 1.0 && fabs(yi) <= 1.0) {
-      o.axis = 0; o.sign = xi > 0 ? 1 : -1; minor = yi;
-    } else if (fabs(yi) == 1.0 && fabs(xi) <= 1.0) {
-      o.axis = 1; o.sign = yi > 0 ? 1 : -1; minor = xi;
-    } else {
-      return fail(MC_EINVAL, "beam %d is not a normalised lidar.py increment (%g, %g)", b, xi, yi);
-    }
-    o.msign = minor > 0 ? 1 : (minor < 0 ? -1 : 0);
-    o.bits = 0;
-    if (!(di >= 1.0)) return fail(MC_EINVAL, "beam %d distinc %g < 1", b, di);
-    // currdist = 0; while currdist < range: currdist += distinc  (lidar.py:49-56)
-    double dist = 0.0;
-    int K = 0;
-    while (dist < E->range && K <= 64) { dist += di; ++K; }
-    if (K > E->s.H)
-      return fail(MC_EINVAL, "beam %d takes %d steps > window half-width %d", b, K, E->s.H);
-    o.K = K;
-    kmax = K > kmax ? K : kmax;
-    kmin = K < kmin ? K : kmin;
-    // the reference's minor-coordinate chain (currx/curry += inc, int() of it)
-    // from every integer start; valid starts are the padded-grid interior
-    const int cm = o.axis == 0 ? E->s.Lp : E->s.Wp;
-    for (int c0 = 0; c0 < cm; ++c0) {
-      double m = (double)c0;
-      int cell = c0;
-      uint64_t w = 0;
-      for (int k = 0; k < K; ++k) {
-        m += minor;
-        const int next = (int)m;  // trunc toward zero, as Python int()
-        const int d = next - cell;
-        if (d != 0 && d != o.msign) {
-          if (m >= 0.0)  // negative coordinates lie outside the grid: unused
-            return fail(MC_EINVAL, "beam %d start %d: minor step %d at k=%d", b, c0, d, k);
-        }
-        if (d != 0) w |= 1ull << k;
-        cell = next;
-      }
-      bits[(size_t)b * cmax + c0] = w;
-    }
-    // the pattern of most starts; it stands for the beam's table when every
-    // start a robot can occupy (1 .. cm-2: the border is -1) visits the same
-    // cells with it up to the first border cell of the minor axis, where the
-    // march ends (an obstacle) -- then the rest of the word is never read.
-    // A beam without such a pattern is flagged (axis bit 1) and marches from
-    // its per-start table (C4's 360 beams: 2 of them, 270 and 315 degrees,
-    // whose float64 chains truncate differently at starts 1..3)
-    {
-      bool bc = true;
-      const uint64_t* row = &bits[(size_t)b * cmax];
-      uint64_t best = row[cm > 2 ? 1 : 0];
-      int best_n = 0;
-      for (int c0 = 1; c0 + 1 < cm; ++c0) {
-        int n = 0;
-        for (int c1 = 1; c1 + 1 < cm; ++c1) n += row[c1] == row[c0];
-        if (n > best_n) { best_n = n; best = row[c0]; }
-        if (2 * n > cm) break;
-      }
-      o.bits = (uint32_t)best;
-      for (int c0 = 1; c0 + 1 < cm && bc; ++c0) {
-        int a = c0, c = c0;  // cell of the start's own word / of the common word
-        for (int k = 0; k < K; ++k) {
-          a += ((row[c0] >> k) & 1) ? o.msign : 0;
-          c += ((best >> k) & 1) ? o.msign : 0;
-          if (a != c) { bc = false; break; }
-          if (a <= 0 || a >= cm - 1) break;  // border reached: the march ends here
-        }
-      }
-      if (!bc) o.axis |= 2;
-      common = common && bc;
-    }
-  }
+  mc::BeamTables T;
+  std::string err;
+  if (!mc::compile_beams(host_table, num_beams, E->range, s.H, s.Wp, s.Lp, T, err))
+    return fail(MC_EINVAL, "%s", err.c_str());
   HIP_TRY(hipSetDevice(E->device));
   // a queued launch (on any stream) may still read the tables: let it finish
   // before they are overwritten or freed.  Until the new tables are complete
@@ -840,91 +442,57 @@ int mc_set_beam_table(void* env, const double* host_table, int32_t num_beams) {
   // rather than reading freed or half-written tables).
   HIP_TRY(hipDeviceSynchronize());
   E->beams_set = false;
-  E->s.fan_nsec = E->s.fan_nspec = E->s.fan_kt = E->s.fan_words = 0;
-  E->s.fan_data = nullptr;
-  E->s.ray_prog = nullptr;
-  E->s.vis_tab = nullptr;
-  if (num_beams != E->beam_count || !E->beams_buf) {
+  s.fan_nsec = s.fan_nspec = s.fan_kt = s.fan_words = 0;
+  s.fan_data = nullptr;
+  s.ray_prog = nullptr;
+  s.vis_tab = nullptr;
+  const size_t bt_bytes = (size_t)num_beams * sizeof(mc::Beam), bits_bytes = T.bits.size() * sizeof(uint64_t);
+  if (num_beams != E->beam_count || !E->beams.p) {
     // the reference lets callers swap _thetalist after construction
     // (even beam counts): (re-)size the device tables
     E->beam_count = 0;
-    if (E->beams_buf) (void)hipFree(E->beams_buf);
-    if (E->bits_buf) (void)hipFree(E->bits_buf);
-    E->beams_buf = E->bits_buf = nullptr;
-    HIP_TRY(hipMalloc(&E->beams_buf, (size_t)num_beams * sizeof(mc::Beam)));
-    HIP_TRY(hipMalloc(&E->bits_buf, bits.size() * sizeof(uint64_t)));
+    E->beams.release();
+    E->bits.release();
+    HIP_TRY(E->beams.reserve(bt_bytes));
+    HIP_TRY(E->bits.reserve(bits_bytes));
     E->beam_count = num_beams;
-    E->s.beams = (const mc::Beam*)E->beams_buf;
-    E->s.beam_bits = (const uint64_t*)E->bits_buf;
-    E->s.bcmax = cmax;
-    E->s.nbeams = num_beams;
-    E->s.mg_nb = mc::magic_div((uint32_t)num_beams);
+    s.beams = (const mc::Beam*)E->beams.p;
+    s.beam_bits = (const uint64_t*)E->bits.p;
+    s.bcmax = T.cmax;
+    s.nbeams = num_beams;
+    s.mg_nb = mc::magic_div((uint32_t)num_beams);
     E->cfg.num_beams = num_beams;
     set_launch_shape(E);
   }
-  HIP_TRY(hipMemcpy((void*)E->s.beams, bt.data(), (size_t)num_beams * sizeof(mc::Beam),
-                    hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy((void*)E->s.beam_bits, bits.data(), bits.size() * sizeof(uint64_t),
-                    hipMemcpyHostToDevice));
-  E->s.beam_kmax = kmax;
-  E->s.beam_kmin = kmin;
-  E->s.beam_common = common && !getenv("MARLCOV_BEAM_TABLE") ? 1 : 0;
-  // step-1 cells of the common patterns (lidar.py:52-56: every beam with
-  // K >= 1 reaches its step-1 cell from the free robot cell)
-  uint32_t k1 = 1u << 4;  // the robot cell (step 0)
-  for (int b = 0; b < num_beams; ++b) {
-    const mc::Beam& o = bt[b];
-    if (o.K < 1) continue;
-    const int mv = (o.bits & 1u) ? o.msign : 0;
-    const int dx = (o.axis & 1) == 0 ? o.sign : mv, dy = (o.axis & 1) == 0 ? mv : o.sign;
-    k1 |= 1u << (3 * (dx + 1) + (dy + 1));
-  }
-  E->s.beam_k1 = E->s.beam_common && !getenv("MARLCOV_NO_K1") ? k1 : 0u;
+  HIP_TRY(hipMemcpy(E->beams.p, T.bt.data(), bt_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(E->bits.p, T.bits.data(), bits_bytes, hipMemcpyHostToDevice));
+  // MARLCOV_BEAM_TABLE: march from the per-start tables, no fan; MARLCOV_NO_K1:
+  // no step-1 premark; MARLCOV_FAN=0: the ray march (parity A/B), per call
+  const bool per_start = getenv("MARLCOV_BEAM_TABLE") != nullptr, no_k1 = getenv("MARLCOV_NO_K1") != nullptr;
+  const bool fan_off = per_start || mc::env_starts_0("MARLCOV_FAN");
+  s.beam_kmax = T.kmax;
+  s.beam_kmin = T.kmin;
+  s.beam_common = T.common && !per_start ? 1 : 0;
+  s.beam_k1 = s.beam_common && !no_k1 ? T.k1 : 0u;
   // ray programs of the launch geometry (set_launch_shape above, or
   // mc_create's: only a new beam count changes it), for common patterns
-  if (E->s.beam_common) {
-    std::vector<uint32_t> rp;
-    const int epw = launch_epw(E);
-    if (mc::build_ray_prog(bt, E->s.N, mc::ray_lpe(E->nt, epw), mc::ray_rpl(E->nt, epw, E->s.N, num_beams), kmax,
-                           E->s.TW <= 4 ? 4 : 8, rp)) {
-      if (rp.size() > E->rayprog_cap) {
-        if (E->rayprog_buf) (void)hipFree(E->rayprog_buf);
-        E->rayprog_buf = nullptr;
-        E->rayprog_cap = 0;
-        HIP_TRY(hipMalloc(&E->rayprog_buf, rp.size() * 4));
-        E->rayprog_cap = rp.size();
-      }
-      HIP_TRY(hipMemcpy(E->rayprog_buf, rp.data(), rp.size() * 4, hipMemcpyHostToDevice));
-      E->s.ray_prog = (const uint32_t*)E->rayprog_buf;
-    }
+  std::vector<uint32_t> words;
+  if (const int epw = s.beam_common ? launch_epw(E) : 0;
+      epw && mc::build_ray_prog(T.bt, s.N, mc::ray_lpe(E->nt, epw), mc::ray_rpl(E->nt, epw, s.N, num_beams), T.kmax, rb,
+                                words)) {
+    if (int rc = upload_words(E->rayprog, words); rc != MC_OK) return rc;
+    s.ray_prog = (const uint32_t*)E->rayprog.p;
   }
-  // fan march of a dense set (after nt / epw: they bound the special lanes);
-  // MARLCOV_FAN=0 or MARLCOV_BEAM_TABLE keep the ray march (parity A/B)
-  {
-    std::vector<uint32_t> fd;
-    int nsec = 0, nspec = 0;
-    const char* fv = getenv("MARLCOV_FAN");
-    bool on = !getenv("MARLCOV_BEAM_TABLE") && !(fv && fv[0] == '0') &&
-              build_fan(bt, bits, cmax, E->s.Wp, E->s.Lp, kmax, E->s.N, E->nt / E->epw, fd, nsec, nspec);
-    const int rb = E->s.TW <= 4 ? 4 : 8;
-    if (on && mc::env_lds_bytes(E->s.N, E->s.TW, num_beams, rb,
-                                mc::fan_lds_bytes(E->s.N, nspec, kmax, (int)fd.size())) > 65536)
-      on = false;
-    if (on) {
-      if (fd.size() > E->fan_cap) {
-        if (E->fan_buf) (void)hipFree(E->fan_buf);
-        E->fan_buf = nullptr;
-        E->fan_cap = 0;
-        HIP_TRY(hipMalloc(&E->fan_buf, fd.size() * 4));
-        E->fan_cap = fd.size();
-      }
-      HIP_TRY(hipMemcpy(E->fan_buf, fd.data(), fd.size() * 4, hipMemcpyHostToDevice));
-      E->s.fan_data = (const uint32_t*)E->fan_buf;
-      E->s.fan_nsec = nsec;
-      E->s.fan_nspec = nspec;
-      E->s.fan_kt = kmax;
-      E->s.fan_words = (int)fd.size();
-    }
+  // fan march of a dense set (after nt / epw: they bound the special lanes)
+  int nsec = 0, nspec = 0;
+  if (!fan_off && mc::build_fan(T, s.Wp, s.Lp, s.N, E->nt / E->epw, words, nsec, nspec) &&
+      mc::env_lds_bytes(s.N, s.TW, num_beams, rb, mc::fan_lds_bytes(s.N, nspec, T.kmax, (int)words.size())) <= 65536) {
+    if (int rc = upload_words(E->fan, words); rc != MC_OK) return rc;
+    s.fan_data = (const uint32_t*)E->fan.p;
+    s.fan_nsec = nsec;
+    s.fan_nspec = nspec;
+    s.fan_kt = T.kmax;
+    s.fan_words = (int)words.size();
   }
   E->beams_set = true;
   // the visibility table of the new beams (the null stream; done before the
@@ -985,10 +553,7 @@ int mc_random_actions(void* env, uint64_t seed, int32_t step, uint8_t* dev_actio
 
 const char* mc_kernel_variant(void* env) {
   Env* E = as_env(env);
-  if (!E) {
-    fail(MC_EINVAL, "mc_kernel_variant: null env");
-    return "";
-  }
+  if (!E) return mc::fail_str(MC_EINVAL, "mc_kernel_variant: null env");
   // the lidar's march: "+fan(S/P)" = fan_march over S sectors and P special
   // beams (dense beam sets), else the ray march
   thread_local std::string name;
@@ -1000,22 +565,14 @@ const char* mc_kernel_variant(void* env) {
 
 const char* mc_kernel_label(void* env) {
   Env* E = as_env(env);
-  if (!E) {
-    fail(MC_EINVAL, "mc_kernel_label: null env");
-    return "";
-  }
+  if (!E) return mc::fail_str(MC_EINVAL, "mc_kernel_label: null env");
   return mc::env_label(E->s, E->nt, launch_epw(E));
 }
 
 const char* mc_dijkstra_variant(void* env) {
   Env* E = as_env(env);
-  if (!E) {
-    fail(MC_EINVAL, "mc_dijkstra_variant: null env");
-    return "";
-  }
-  if (!E->cfg.dijkstra_input) return "";
-  if (E->dj_window) return E->dj_big ? "window+hbm" : "window+lds";
-  return E->dj_big ? "hbm" : "lds";
+  if (!E) return mc::fail_str(MC_EINVAL, "mc_dijkstra_variant: null env");
+  return E->cfg.dijkstra_input ? bfs_name(E->dj_window, E->dj_big) : "";
 }
 
 static_assert(mc::kFrontierEinval == MC_EINVAL && mc::kFrontierEstate == MC_ESTATE && mc::kActStay == MC_ACT_STAY,
@@ -1029,47 +586,20 @@ int mc_frontier_setup(void* env) {
   if (ck.rc) return fail(ck.rc, "%s", ck.msg);
   if (E->fr_setup) return MC_OK;
   const mc::State& s = E->s;
-  const int pad = E->cfg.pad;
   HIP_TRY(hipSetDevice(E->device));
-  const size_t need = mc::dijkstra_lds_bytes(s, pad);
-  int maxlds = 0;
-  if (hipDeviceGetAttribute(&maxlds, hipDeviceAttributeMaxSharedMemoryPerBlock, E->device) != hipSuccess)
-    return fail(MC_EHIP, "mc_frontier_setup: cannot query the device's LDS per workgroup");
-  const char* fb = getenv("MARLCOV_DJ_BIG");
-  const bool big = need + 1024 > (size_t)maxlds || (fb && atoi(fb) == 1);
-  size_t added = 0;
-  uint64_t* scratch = nullptr;
-  unsigned slots = 0;
-  if (big && E->dj_big) {  // a dijkstra_input handle's scratch, sized by the same rule
-    scratch = E->dj_big;
-    slots = E->dj_big_slots;
-  } else if (big) {
-    slots = mc::dijkstra_big_slots(s, pad);
-    const size_t bytes = (size_t)slots * mc::dijkstra_big_slot_bytes(s, pad);
-    void* bq = nullptr;
-    if (dev_alloc(E, &bq, bytes) != MC_OK) {
-      std::string msg = g_err;
-      return fail(MC_EHIP, "mc_frontier_setup: %zu B of scratch (%u slots) for a %dx%d grid: %s", bytes, slots,
-                  E->cfg.width, E->cfg.length, msg.c_str());
-    }
-    scratch = (uint64_t*)bq;
-    added += bytes;
-  } else if (need > 65536) {
-    HIP_TRY(mc::frontier_allow_lds(need));
-  }
-  void* lq = nullptr;
-  const size_t list_bytes = ((size_t)s.B * s.N + 3) * 4;
-  if (dev_alloc(E, &lq, list_bytes) != MC_OK) {
-    std::string msg = g_err;
-    return fail(MC_EHIP, "mc_frontier_setup: item list: %s", msg.c_str());
-  }
-  added += list_bytes;
-  E->fr_list = (uint32_t*)lq;
-  E->fr_big = scratch;
-  E->fr_big_slots = slots;
-  const char* fo = getenv("MARLCOV_DJ_FULL");
-  E->fr_window = !(fo && atoi(fo) == 1);
-  E->lay.state_bytes += (int64_t)added;
+  // a dijkstra_input handle's scratch, sized by the same rule, serves both
+  size_t need = 0;
+  uint64_t* scratch = E->dj_big;
+  unsigned slots = E->dj_big_slots;
+  if (int rc = choose_bfs(E, "mc_frontier_setup", &need, scratch, slots); rc != MC_OK) return rc;
+  if (need > 65536) HIP_TRY(mc::frontier_allow_lds(need));
+  const size_t list_words = (size_t)s.B * s.N + 3;
+  if (mc::dev_alloc(E->allocs, E->fr_list, list_words) != MC_OK)
+    return fail(MC_EHIP, "mc_frontier_setup: item list: %s", mc::g_last_error.c_str());
+  E->lay.state_bytes += (int64_t)list_words * 4;
+  E->fr_big = need ? nullptr : scratch;
+  E->fr_big_slots = need ? 0 : slots;
+  E->fr_window = !mc::env_is_1("MARLCOV_DJ_FULL");
   HIP_TRY(hipDeviceSynchronize());  // the zeroed count words are there before any stream's first call
   E->fr_setup = true;
   return MC_OK;
@@ -1078,13 +608,8 @@ int mc_frontier_setup(void* env) {
 const char* mc_frontier_variant(void* env) {
   Env* E = as_env(env);
   const mc::FrontierCheck ck = mc::frontier_check_variant(E);
-  if (ck.rc) {
-    fail(ck.rc, "%s", ck.msg);
-    return "";
-  }
-  if (!E->fr_setup) return "";
-  if (E->fr_window) return E->fr_big ? "window+hbm" : "window+lds";
-  return E->fr_big ? "hbm" : "lds";
+  if (ck.rc) return mc::fail_str(ck.rc, ck.msg);
+  return E->fr_setup ? bfs_name(E->fr_window, E->fr_big) : "";
 }
 
 int mc_frontier_actions(void* env, uint8_t* dev_actions, int32_t* dev_dist, int32_t* dev_goal, void* stream) {
@@ -1242,11 +767,9 @@ int mc_step_many(void* env, const uint8_t* dev_actions, int64_t actions_stride, 
                    reinterpret_cast<double*>(reinterpret_cast<char*>(dev_reward) + k * reward_stride),
                    dev_done + k * done_stride, static_cast<char*>(dev_obs) + k * obs_stride,
                    dev_adj ? dev_adj + k * adj_stride : nullptr, st);
-    if (rc) {  // steps 0..k-1 are enqueued: the env has advanced k steps
-      std::string msg = g_err;
+    if (rc)  // steps 0..k-1 are enqueued: the env has advanced k steps
       return fail(rc, "mc_step_many: step %d of %d failed after %d steps were enqueued: %s", (int)k,
-                  (int)num_steps, (int)k, msg.c_str());
-    }
+                  (int)num_steps, (int)k, mc::g_last_error.c_str());
   }
   return MC_OK;
 }

@@ -112,7 +112,7 @@ struct EnvCfg {
   static constexpr bool OBS_FAST = ObsFast<SH::EGO, SH::N, SH::LC>::ok && (NT == 64 || EPW == 1) &&
                                    ObsFast<SH::EGO, SH::N, SH::LC>::NB <= 64;
   static constexpr int NS_OBS = (SH::N > 0 && SH::N <= 16) ? SH::N : 0;
-  // the march from the host-built ray programs (mc_internal.h build_ray_prog;
+  // the march from the host-built ray programs (mc_beams.h build_ray_prog;
   // select_env_row: State::ray_prog is set): compiled sparse-beam shapes of up
   // to 8 agents with one wave per workgroup whose rays take one pass -- no beam
   // records in LDS, no ray_init, no ray_advance chain.  Without a program

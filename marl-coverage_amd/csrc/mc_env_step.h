@@ -1342,7 +1342,7 @@ __device__ __forceinline__ void sense(const State& s, const CT& C) {
     const uint32_t sink_m = (uint32_t)(uintptr_t)(const lds_char*)(const char*)sink -
                             (uint32_t)((L.fpr - L.negr) * (int)sizeof(WT));
     if constexpr (CT::RAYPROG) {
-      // the lane's rays from its program row (C.rp: build_ray_prog): the
+      // the lane's rays from its program row (C.rp: mc_beams.h build_ray_prog): the
       // cell of ray j at step k is its agent's P0 plus a 16-bit offset -- one
       // sign-extending add and the address shift per ray and step; every row
       // word is read before the first mark, as below

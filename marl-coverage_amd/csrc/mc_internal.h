@@ -5,8 +5,6 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include <vector>
-
 namespace mc {
 
 enum Mode : int { MODE_STEP = 0, MODE_RESET = 1 };
@@ -121,7 +119,7 @@ struct State {
   // instead of once per ray (0 = no premark, the march marks step 1)
   uint32_t beam_k1;
   // Fan march of a dense beam set (mc_env_step.h fan_march; built by
-  // mc_set_beam_table, off when fan_nsec + fan_nspec == 0).  fan_data: the
+  // mc_beams.h build_fan, off when fan_nsec + fan_nspec == 0).  fan_data: the
   // spread / expand LUTs (kFanLutBytes), fan_nsec / 2 sector-pair records of
   // 2 (fan_kt + 1) words (the two sectors of one line, interleaved: words 0, 1
   // their FAN_* class bits, words 2k, 2k + 1 their step-k entries) and
@@ -196,8 +194,8 @@ struct State {
   // clears the counters): percent_covered() and _currstep at the end
   double* ep_pc;
   int32_t* ep_len;
-  // Ray programs of the sparse-beam march (build_ray_prog; null: none, the
-  // compiled sparse-beam kernels are then not selected): one row of
+  // Ray programs of the sparse-beam march (mc_beams.h build_ray_prog; null:
+  // none, the compiled sparse-beam kernels are then not selected): one row of
   // ray_prog_row_words words per lane of an env slot
   const uint32_t* ray_prog;
   // The lidar's visibility table (mc_vistab.h; null: none, the kernels march):
@@ -314,18 +312,9 @@ __host__ __device__ constexpr int ray_rpl(int nt, int epw, int n, int nb) {
   return ray_rplk(nt, epw, n, nb) > 0 ? ray_rplk(nt, epw, n, nb) : ray_rpl0(epw);
 }
 
-// Ray program: what ray_init and the read phase's ray_advance chain would
-// compute for a lane's rays, built once per beam table and launch geometry
-// (with common step bits a ray's cell at step k sits at a fixed offset from
-// its agent's cell).  Lane `sub` of a slot marches rays idx = sub * rpl + j
-// (j < rpl) of agent idx / nbeams, beam idx % nbeams.  Its row: rpl * km
-// int16 offsets T[j * km + k - 1] (k = 1 .. km), two per word, low half
-// first -- the ray's packed cell (mc_env_step.h struct Ray) at step k is
-// P0(agent) + T; then zero padding to whole 16-byte quads less one word; the
-// last word holds a byte per ray: bits 0-4 K + 1 (0: idx >= N * nbeams, a
-// dead ray), bits 5-7 the agent.  The table is stored by 16-byte quads, quad
-// q of every lane together (word w of lane sub at ray_prog_word): one
-// 16-byte load per lane then reads consecutive memory across the slot.
+// Ray program geometry (layout and builder: mc_beams.h build_ray_prog): words
+// of a lane's row, where word w of lane `sub` is stored (by 16-byte quads
+// across the slot's lanes), and the largest offset a row may hold.
 __host__ __device__ constexpr int ray_prog_row_words(int rpl, int km) { return ((rpl * km + 1) / 2 + 1 + 3) & ~3; }
 __host__ __device__ constexpr size_t ray_prog_word(int lpe, int sub, int w) {
   return ((size_t)(w >> 2) * lpe + sub) * 4 + (w & 3);
@@ -333,46 +322,6 @@ __host__ __device__ constexpr size_t ray_prog_word(int lpe, int sub, int w) {
 // largest |T|: km steps of one window row and one column each
 __host__ __device__ constexpr int ray_prog_span(int N, int rowbytes, int km) {
   return km * (row_step_words(N, rowbytes) * rowbytes * 64 + 1);
-}
-
-// The ray programs of every lane of a slot (lpe rows).  False (out empty)
-// when the table cannot hold them: more than one pass of rays, more than 8
-// agents, a K that does not fit its field or an offset beyond int16.  Plain
-// host code (no HIP call).
-inline bool build_ray_prog(const std::vector<Beam>& bt, int N, int lpe, int rpl, int km, int rowbytes,
-                           std::vector<uint32_t>& out) {
-  out.clear();
-  const int nb = (int)bt.size(), total = N * nb;
-  if (nb < 1 || N < 1 || N > 8 || km < 1 || km > 30 || rpl < 1 || rpl > 4 || total > lpe * rpl) return false;
-  if (ray_prog_span(N, rowbytes, km) > 32767) return false;
-  const int rw = ray_prog_row_words(rpl, km);
-  const int RB = row_step_words(N, rowbytes) * rowbytes * 64;  // one window row in P units
-  out.assign((size_t)lpe * rw, 0u);
-  for (int sub = 0; sub < lpe; ++sub) {
-    std::vector<uint32_t> row((size_t)rw, 0u);
-    for (int j = 0; j < rpl; ++j) {
-      const int idx = sub * rpl + j;
-      if (idx >= total) continue;  // dead ray: K + 1 = 0, agent 0, offsets 0
-      const int a = idx / nb;
-      const Beam& bm = bt[idx - a * nb];
-      if (bm.K < 0 || bm.K > km) { out.clear(); return false; }
-      const bool ax = (bm.axis & 1) == 0;
-      // ray_init's d0 / d1, and ray_advance's chain in its 32-bit arithmetic
-      const uint32_t d0 = (uint32_t)(ax ? bm.sign * RB : bm.sign);
-      const uint32_t d1 = (uint32_t)(ax ? bm.msign : bm.msign * RB);
-      uint32_t t = 0;
-      for (int k = 1; k <= km; ++k) {
-        t += d0 + ((0u - ((bm.bits >> (k - 1)) & 1u)) & d1);
-        const int32_t v = (int32_t)t;
-        if (v < -32768 || v > 32767) { out.clear(); return false; }
-        const int i = j * km + k - 1;
-        row[i >> 1] |= (uint32_t)(uint16_t)(int16_t)v << (16 * (i & 1));
-      }
-      row[rw - 1] |= ((uint32_t)(bm.K + 1) | ((uint32_t)a << 5)) << (8 * j);
-    }
-    for (int w = 0; w < rw; ++w) out[ray_prog_word(lpe, sub, w)] = row[w];
-  }
-  return true;
 }
 
 // Fan march (mc_env_step.h fan_march): sectors of up to kFanS adjacent

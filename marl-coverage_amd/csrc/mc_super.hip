@@ -34,22 +34,17 @@
 // vs real cv2 unpinned.
 #include <hip/hip_runtime.h>
 
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 
-#include <string>
+#include <memory>
 #include <vector>
 
 #include "marlcov.h"
 #include "mc_device.h"
 #include "mc_fork.h"
 #include "mc_fuse.h"
-
-namespace mc {
-void set_last_error(const char* msg);
-}
+#include "mc_host.h"
 
 namespace mcs {
 
@@ -1321,22 +1316,7 @@ __global__ void sg_gen_kernel(SState s, uint64_t seed, uint32_t thresh, uint64_t
 // ==========================================================================
 namespace {
 
-int sg_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int sg_fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  mc::set_last_error(buf);
-  return code;
-}
-
-#define SG_TRY(expr)                                                                       \
-  do {                                                                                     \
-    hipError_t _e = (expr);                                                                \
-    if (_e != hipSuccess) return sg_fail(MC_EHIP, "%s: %s", #expr, hipGetErrorString(_e)); \
-  } while (0)
+using mc::fail;
 
 // Every step kernel mc_sg_step can launch, with the name mc_sg_kernel_variant
 // and mc_sg_kernel_name report for it.
@@ -1410,16 +1390,6 @@ const SgKernel* sg_select(const SgEnv* E) {
 
 SgEnv* as_sg(void* p) { return static_cast<SgEnv*>(p); }
 
-int sg_alloc(SgEnv* E, void** p, size_t bytes) {
-  void* q = nullptr;
-  SG_TRY(hipMalloc(&q, bytes < 16 ? 16 : bytes));
-  SG_TRY(hipMemset(q, 0, bytes < 16 ? 16 : bytes));
-  E->allocs.push_back(q);
-  E->lay.state_bytes += (int64_t)bytes;
-  *p = q;
-  return MC_OK;
-}
-
 struct SgField {
   void* ptr;
   int64_t bytes;
@@ -1448,8 +1418,8 @@ SgField sg_field(SgEnv* E, int f) {
 }
 
 int sg_ready(SgEnv* E, const char* who) {
-  if (!E->grids_set) return sg_fail(MC_ESTATE, "%s: grids not set (mc_sg_set_grids / mc_sg_generate_grids)", who);
-  if (!E->s.planes || !E->s.dist_plane) return sg_fail(MC_ESTATE, "%s: state buffers not registered (mc_sg_set_obs)", who);
+  if (!E->grids_set) return fail(MC_ESTATE, "%s: grids not set (mc_sg_set_grids / mc_sg_generate_grids)", who);
+  if (!E->s.planes || !E->s.dist_plane) return fail(MC_ESTATE, "%s: state buffers not registered (mc_sg_set_obs)", who);
   return MC_OK;
 }
 
@@ -1481,11 +1451,11 @@ hipError_t launch_step(SgEnv* E, const uint8_t* actions, const int32_t* quot, do
 
 int check_numpos(SgEnv* E, hipStream_t st) {
   std::vector<int32_t> np(E->s.G);
-  SG_TRY(hipMemcpyAsync(np.data(), E->s.numpos, np.size() * 4, hipMemcpyDeviceToHost, st));
-  SG_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpyAsync(np.data(), E->s.numpos, np.size() * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   for (int g = 0; g < E->s.G; ++g)
     if (np[g] <= 0)
-      return sg_fail(MC_EINVAL,
+      return fail(MC_EINVAL,
                      "grid %d has no cell > 0: percent_covered() divides by count_nonzero(grid > 0) "
                      "(super_grid_rl.py:420-421)",
                      g);
@@ -1498,17 +1468,17 @@ int check_numpos(SgEnv* E, hipStream_t st) {
 extern "C" {
 
 int mc_sg_create(const mc_sg_config* cfg, int hip_device, void** out_env) {
-  if (!cfg || !out_env) return sg_fail(MC_EINVAL, "mc_sg_create: null argument");
+  if (!cfg || !out_env) return fail(MC_EINVAL, "mc_sg_create: null argument");
   const mc_sg_config& c = *cfg;
-  if (c.num_envs < 1) return sg_fail(MC_EINVAL, "num_envs must be >= 1");
-  if (c.num_agents < 1 || c.num_agents > mcs::kMaxAgents) return sg_fail(MC_EINVAL, "numrobot must be in [1, 64]");
+  if (c.num_envs < 1) return fail(MC_EINVAL, "num_envs must be >= 1");
+  if (c.num_agents < 1 || c.num_agents > mcs::kMaxAgents) return fail(MC_EINVAL, "numrobot must be in [1, 64]");
   if (c.width < 1 || c.length < 1 || c.width > mcs::kMaxSide || c.length > mcs::kMaxSide)
-    return sg_fail(MC_EINVAL, "grid sides must be in [1, %d]", mcs::kMaxSide);
-  if ((int64_t)c.width * c.length < c.num_agents) return sg_fail(MC_EINVAL, "more robots than cells");
-  if (c.num_grids < 1) return sg_fail(MC_EINVAL, "num_grids must be >= 1");
-  if (c.senseradius < 0 || c.senseradius > mcs::kMaxRadius) return sg_fail(MC_EINVAL, "senseradius must be in [0, 15]");
-  SG_TRY(hipSetDevice(hip_device));
-  SgEnv* E = new SgEnv();
+    return fail(MC_EINVAL, "grid sides must be in [1, %d]", mcs::kMaxSide);
+  if ((int64_t)c.width * c.length < c.num_agents) return fail(MC_EINVAL, "more robots than cells");
+  if (c.num_grids < 1) return fail(MC_EINVAL, "num_grids must be >= 1");
+  if (c.senseradius < 0 || c.senseradius > mcs::kMaxRadius) return fail(MC_EINVAL, "senseradius must be in [0, 15]");
+  HIP_TRY(hipSetDevice(hip_device));
+  std::unique_ptr<SgEnv, mc::HandleDeleter<mc_sg_destroy>> E(new SgEnv());
   E->cfg = c;
   E->device = hip_device;
   E->lay = mc_sg_layout{};
@@ -1532,29 +1502,22 @@ int mc_sg_create(const mc_sg_config* cfg, int hip_device, void** out_env) {
   s.auto_reset = c.auto_reset != 0;
   s.grid_mode = c.reset_grid_mode;
   s.mg_L = mc::magic_div((uint32_t)c.length);
-  {
-    const char* fd = getenv("MARLCOV_SG_FULL_DIST");
-    s.dist_full = fd && atoi(fd) == 1;
-    // MARLCOV_SG_ROWS=0: one lane per robot instead of the row-parallel step
-    // kernel (read per handle: the parity suite runs both)
-    const char* rw = getenv("MARLCOV_SG_ROWS");
-    E->rows = !(rw && atoi(rw) == 0);
-    // the A/B knobs of the step and distance kernels, per handle as well
-    const char* gp = getenv("MARLCOV_SG_GPW");
-    E->gpw_cap = gp && atoi(gp) >= 1 ? atoi(gp) : 4;
-    const char* ge = getenv("MARLCOV_SG_GENERIC");
-    E->force_generic = ge && atoi(ge) == 1;
-    const char* sw = getenv("MARLCOV_SG_SWEEP");
-    E->force_sweep = sw && atoi(sw) == 1;
-    // steps per fused mc_sg_step_many launch: mc_step_many's variable, parser and limits
-    E->fuse_steps = mc::fuse_steps_from_env(getenv("MARLCOV_FUSE_STEPS"));
-  }
-  E->step = sg_select(E);
-  if (!E->step) {
-    delete E;
-    return sg_fail(MC_EINVAL, "mc_sg_create: no step kernel for numrobot %d, senseradius %d", c.num_agents,
-                   c.senseradius);
-  }
+  s.dist_full = mc::env_is_1("MARLCOV_SG_FULL_DIST");
+  // MARLCOV_SG_ROWS=0: one lane per robot instead of the row-parallel step
+  // kernel (read per handle: the parity suite runs both)
+  const char* rw = getenv("MARLCOV_SG_ROWS");
+  E->rows = !(rw && atoi(rw) == 0);
+  // the A/B knobs of the step and distance kernels, per handle as well
+  const char* gp = getenv("MARLCOV_SG_GPW");
+  E->gpw_cap = gp && atoi(gp) >= 1 ? atoi(gp) : 4;
+  E->force_generic = mc::env_is_1("MARLCOV_SG_GENERIC");
+  E->force_sweep = mc::env_is_1("MARLCOV_SG_SWEEP");
+  // steps per fused mc_sg_step_many launch: mc_step_many's variable, parser and limits
+  E->fuse_steps = mc::fuse_steps_from_env(getenv("MARLCOV_FUSE_STEPS"));
+  E->step = sg_select(E.get());
+  if (!E->step)
+    return fail(MC_EINVAL, "mc_sg_create: no step kernel for numrobot %d, senseradius %d", c.num_agents,
+                c.senseradius);
   s.seed = c.seed;
   s.env0 = c.env_offset;
   s.grid0 = c.grid_offset;
@@ -1568,52 +1531,28 @@ int mc_sg_create(const mc_sg_config* cfg, int hip_device, void** out_env) {
   const int side = c.width > c.length ? c.width : c.length;
   E->dist_nt = side <= 64 ? 64 : (side <= 128 ? 128 : 256);
   const size_t B = s.B, N = s.N, G = s.G, mw = (size_t)s.W * s.RW;
-  void* p;
-  int rc = 0;
-#define SG_ALLOC(field, type, bytes)        \
-  rc = sg_alloc(E, &p, (bytes));            \
-  if (rc) { mc_sg_destroy(E); return rc; }  \
-  s.field = (type)p;
-  SG_ALLOC(gneg, const uint64_t*, G * mw * 8);
-  SG_ALLOC(gpos, const uint64_t*, G * mw * 8);
-  SG_ALLOC(numpos, const int32_t*, G * 4);
-  SG_ALLOC(env_grid, int32_t*, B * 4);
-  SG_ALLOC(pos, int32_t*, B * N * 8);
-  SG_ALLOC(cov, uint64_t*, B * mw * 8);
-  SG_ALLOC(obst, uint64_t*, B * mw * 8);
-  SG_ALLOC(cov_cnt, uint32_t*, B * 4);
-  SG_ALLOC(currstep, int32_t*, B * 4);
-  SG_ALLOC(done_thresh, double*, B * 8);
-  SG_ALLOC(a_prev, int32_t*, B * 4);
-  SG_ALLOC(episode, uint32_t*, B * 4);
-  SG_ALLOC(full, uint8_t*, B);
-  SG_ALLOC(dist_M, int32_t*, B * 4);
-  SG_ALLOC(ep_pc, double*, B * 8);
-  SG_ALLOC(ep_len, int32_t*, B * 4);
-  SG_ALLOC(err, uint32_t*, 4);
-  if (!E->lds) {
-    SG_ALLOC(scratch, uint16_t*, B * s.W * E->pitch * 2);
-  }
-#undef SG_ALLOC
-  {
-    std::vector<int32_t> eg(B), ap(B, -1);
-    std::vector<double> dt(B, c.done_thresh);
-    std::vector<uint8_t> fl(B, 1);
-    for (size_t e = 0; e < B; ++e) eg[e] = (int32_t)(e % G);
-    hipError_t he = hipMemcpy(s.env_grid, eg.data(), B * 4, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemcpy(s.a_prev, ap.data(), B * 4, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemcpy(s.done_thresh, dt.data(), B * 8, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemcpy(s.full, fl.data(), B, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemset(s.dist_M, 0xFF, B * 4);
-    if (he != hipSuccess) {
-      mc_sg_destroy(E);
-      return sg_fail(MC_EHIP, "mc_sg_create: %s", hipGetErrorString(he));
-    }
-  }
+  int rc = MC_OK;
+  auto alloc = [&](auto*& dst, size_t count, int fill = 0) {  // state_bytes sums every array
+    E->lay.state_bytes += (int64_t)(count * sizeof(*dst));
+    return rc = mc::dev_alloc(E->allocs, dst, count, fill);
+  };
+  // (a_prev and dist_M start at -1, the full-rewrite flags at 1)
+  if (alloc(s.gneg, G * mw) || alloc(s.gpos, G * mw) || alloc(s.numpos, G) || alloc(s.env_grid, B) ||
+      alloc(s.pos, B * N * 2) || alloc(s.cov, B * mw) || alloc(s.obst, B * mw) || alloc(s.cov_cnt, B) ||
+      alloc(s.currstep, B) || alloc(s.done_thresh, B) || alloc(s.a_prev, B, 0xFF) || alloc(s.episode, B) ||
+      alloc(s.full, B, 1) || alloc(s.dist_M, B, 0xFF) || alloc(s.ep_pc, B) || alloc(s.ep_len, B) ||
+      alloc(s.err, 1) || (!E->lds && alloc(s.scratch, B * s.W * E->pitch)))
+    return rc;
+  std::vector<int32_t> eg(B);
+  std::vector<double> dt(B, c.done_thresh);
+  for (size_t e = 0; e < B; ++e) eg[e] = (int32_t)(e % G);
+  hipError_t he = hipMemcpy(s.env_grid, eg.data(), B * 4, hipMemcpyHostToDevice);
+  if (he == hipSuccess) he = hipMemcpy(s.done_thresh, dt.data(), B * 8, hipMemcpyHostToDevice);
+  if (he != hipSuccess) return fail(MC_EHIP, "mc_sg_create: %s", hipGetErrorString(he));
   E->lay.pos_layers = s.P;
   E->lay.obs_layers = s.P + 2;
   E->lay.row_words = s.RW;
-  *out_env = E;
+  *out_env = E.release();
   return MC_OK;
 }
 
@@ -1627,80 +1566,80 @@ void mc_sg_destroy(void* env) {
 
 int mc_sg_query(void* env, mc_sg_layout* out) {
   SgEnv* E = as_sg(env);
-  if (!E || !out) return sg_fail(MC_EINVAL, "mc_sg_query: null argument");
+  if (!E || !out) return fail(MC_EINVAL, "mc_sg_query: null argument");
   *out = E->lay;
   return MC_OK;
 }
 
 int mc_sg_set_grids(void* env, const int8_t* dev_grids, int32_t num_grids, void* stream) {
   SgEnv* E = as_sg(env);
-  if (!E || !dev_grids) return sg_fail(MC_EINVAL, "mc_sg_set_grids: null argument");
-  if (num_grids != E->s.G) return sg_fail(MC_EINVAL, "mc_sg_set_grids: %d grids, config says %d", num_grids, E->s.G);
+  if (!E || !dev_grids) return fail(MC_EINVAL, "mc_sg_set_grids: null argument");
+  if (num_grids != E->s.G) return fail(MC_EINVAL, "mc_sg_set_grids: %d grids, config says %d", num_grids, E->s.G);
   hipStream_t st = (hipStream_t)stream;
-  SG_TRY(hipSetDevice(E->device));
-  SG_TRY(hipMemsetAsync((void*)E->s.numpos, 0, (size_t)E->s.G * 4, st));
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(hipMemsetAsync((void*)E->s.numpos, 0, (size_t)E->s.G * 4, st));
   const size_t total = (size_t)E->s.G * E->s.W * E->s.RW;
   const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
   hipLaunchKernelGGL(mcs::sg_pack_kernel, dim3(blocks), dim3(256), 0, st, E->s, dev_grids,
                      (uint64_t*)E->s.gneg, (uint64_t*)E->s.gpos, (int32_t*)E->s.numpos);
-  SG_TRY(hipGetLastError());
-  SG_TRY(hipMemsetAsync(E->s.full, 1, (size_t)E->s.B, st));  // new obstacles: every layer value may change
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemsetAsync(E->s.full, 1, (size_t)E->s.B, st));  // new obstacles: every layer value may change
   E->stale = true;
   return check_numpos(E, st);
 }
 
 int mc_sg_generate_grids(void* env, uint64_t seed, double p_obst, void* stream) {
   SgEnv* E = as_sg(env);
-  if (!E) return sg_fail(MC_EINVAL, "mc_sg_generate_grids: null env");
-  if (!(p_obst >= 0.0 && p_obst < 1.0)) return sg_fail(MC_EINVAL, "p_obst must be in [0, 1)");
+  if (!E) return fail(MC_EINVAL, "mc_sg_generate_grids: null env");
+  if (!(p_obst >= 0.0 && p_obst < 1.0)) return fail(MC_EINVAL, "p_obst must be in [0, 1)");
   hipStream_t st = (hipStream_t)stream;
-  SG_TRY(hipSetDevice(E->device));
-  SG_TRY(hipMemsetAsync((void*)E->s.numpos, 0, (size_t)E->s.G * 4, st));
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(hipMemsetAsync((void*)E->s.numpos, 0, (size_t)E->s.G * 4, st));
   const size_t total = (size_t)E->s.G * E->s.W * E->s.RW;
   const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
   const uint32_t thresh = (uint32_t)(p_obst * 4294967296.0);
   hipLaunchKernelGGL(mcs::sg_gen_kernel, dim3(blocks), dim3(256), 0, st, E->s, seed, thresh,
                      (uint64_t*)E->s.gneg, (uint64_t*)E->s.gpos, (int32_t*)E->s.numpos);
-  SG_TRY(hipGetLastError());
-  SG_TRY(hipMemsetAsync(E->s.full, 1, (size_t)E->s.B, st));  // new obstacles: every layer value may change
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemsetAsync(E->s.full, 1, (size_t)E->s.B, st));  // new obstacles: every layer value may change
   E->stale = true;
   return check_numpos(E, st);
 }
 
 int mc_sg_set_env_grids(void* env, const int32_t* dev_env_grid, void* stream) {
   SgEnv* E = as_sg(env);
-  if (!E || !dev_env_grid) return sg_fail(MC_EINVAL, "mc_sg_set_env_grids: null argument");
-  SG_TRY(hipSetDevice(E->device));
-  SG_TRY(hipMemcpyAsync(E->s.env_grid, dev_env_grid, (size_t)E->s.B * 4, hipMemcpyDeviceToDevice,
+  if (!E || !dev_env_grid) return fail(MC_EINVAL, "mc_sg_set_env_grids: null argument");
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(hipMemcpyAsync(E->s.env_grid, dev_env_grid, (size_t)E->s.B * 4, hipMemcpyDeviceToDevice,
                         (hipStream_t)stream));
-  SG_TRY(hipMemsetAsync(E->s.full, 1, (size_t)E->s.B, (hipStream_t)stream));
+  HIP_TRY(hipMemsetAsync(E->s.full, 1, (size_t)E->s.B, (hipStream_t)stream));
   E->stale = true;
   return MC_OK;
 }
 
 int mc_sg_set_obs(void* env, uint8_t* dev_planes, float* dev_dist) {
   SgEnv* E = as_sg(env);
-  if (!E || !dev_planes || !dev_dist) return sg_fail(MC_EINVAL, "mc_sg_set_obs: null argument");
+  if (!E || !dev_planes || !dev_dist) return fail(MC_EINVAL, "mc_sg_set_obs: null argument");
   E->s.planes = dev_planes;
   E->s.dist_plane = dev_dist;
-  SG_TRY(hipSetDevice(E->device));
-  SG_TRY(hipMemset(E->s.full, 1, (size_t)E->s.B));
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(hipMemset(E->s.full, 1, (size_t)E->s.B));
   E->stale = true;
   return MC_OK;
 }
 
 int mc_sg_reset(void* env, const uint8_t* dev_env_mask, const int32_t* dev_pos, void* stream) {
   SgEnv* E = as_sg(env);
-  if (!E) return sg_fail(MC_EINVAL, "mc_sg_reset: null env");
+  if (!E) return fail(MC_EINVAL, "mc_sg_reset: null env");
   int rc = sg_ready(E, "mc_sg_reset");
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  SG_TRY(hipSetDevice(E->device));
+  HIP_TRY(hipSetDevice(E->device));
   const int blocks = (E->s.B + mcs::kEnvsPerBlock - 1) / mcs::kEnvsPerBlock;
   hipLaunchKernelGGL(mcs::sg_reset_kernel, dim3(blocks), dim3(64 * mcs::kEnvsPerBlock), 0, st, E->s,
                      dev_env_mask, dev_pos);
-  SG_TRY(hipGetLastError());
-  SG_TRY(launch_dist(E, st));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_dist(E, st));
   E->stale = false;
   return MC_OK;
 }
@@ -1708,13 +1647,13 @@ int mc_sg_reset(void* env, const uint8_t* dev_env_mask, const int32_t* dev_pos, 
 int mc_sg_step(void* env, const uint8_t* dev_actions, const int32_t* dev_quot, double* dev_reward,
                uint8_t* dev_done, void* stream) {
   SgEnv* E = as_sg(env);
-  if (!E || !dev_actions || !dev_reward || !dev_done) return sg_fail(MC_EINVAL, "mc_sg_step: null argument");
+  if (!E || !dev_actions || !dev_reward || !dev_done) return fail(MC_EINVAL, "mc_sg_step: null argument");
   int rc = sg_ready(E, "mc_sg_step");
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  SG_TRY(hipSetDevice(E->device));
-  if (E->stale) SG_TRY(launch_dist(E, st));  // the pre-move distance_map of the current maps
-  SG_TRY(launch_step(E, dev_actions, dev_quot, dev_reward, dev_done, st));
+  HIP_TRY(hipSetDevice(E->device));
+  if (E->stale) HIP_TRY(launch_dist(E, st));  // the pre-move distance_map of the current maps
+  HIP_TRY(launch_step(E, dev_actions, dev_quot, dev_reward, dev_done, st));
   E->stale = false;
   return MC_OK;
 }
@@ -1723,21 +1662,21 @@ int mc_sg_step_many(void* env, const uint8_t* dev_actions, int64_t actions_strid
                     int64_t quot_stride, int32_t num_steps, double* dev_reward, int64_t reward_stride,
                     uint8_t* dev_done, int64_t done_stride, void* stream) {
   SgEnv* E = as_sg(env);
-  if (!E || !dev_actions || !dev_reward || !dev_done) return sg_fail(MC_EINVAL, "mc_sg_step_many: null argument");
+  if (!E || !dev_actions || !dev_reward || !dev_done) return fail(MC_EINVAL, "mc_sg_step_many: null argument");
   if (num_steps < 0 || actions_stride < 0 || quot_stride < 0 || reward_stride < 0 || done_stride < 0)
-    return sg_fail(MC_EINVAL, "mc_sg_step_many: negative step count or stride");
-  if (reward_stride % 8 != 0) return sg_fail(MC_EINVAL, "mc_sg_step_many: reward_stride must be a multiple of 8 bytes");
-  if (quot_stride % 4 != 0) return sg_fail(MC_EINVAL, "mc_sg_step_many: quot_stride must be a multiple of 4 bytes");
+    return fail(MC_EINVAL, "mc_sg_step_many: negative step count or stride");
+  if (reward_stride % 8 != 0) return fail(MC_EINVAL, "mc_sg_step_many: reward_stride must be a multiple of 8 bytes");
+  if (quot_stride % 4 != 0) return fail(MC_EINVAL, "mc_sg_step_many: quot_stride must be a multiple of 4 bytes");
   // mc_fuse.h's five per-step buffers: the quotients ride in the obs slot, the last stays unused
   const int64_t stride[mc::FUSE_BUFS] = {actions_stride, reward_stride, done_stride, quot_stride, 0};
   if (!mc::fuse_offsets_fit(num_steps, stride))
-    return sg_fail(MC_EINVAL, "mc_sg_step_many: a stride times the step count overflows int64");
+    return fail(MC_EINVAL, "mc_sg_step_many: a stride times the step count overflows int64");
   int rc = sg_ready(E, "mc_sg_step_many");
   if (rc) return rc;
   if (num_steps == 0) return MC_OK;
   hipStream_t st = (hipStream_t)stream;
-  SG_TRY(hipSetDevice(E->device));
-  if (E->stale) SG_TRY(launch_dist(E, st));  // as mc_sg_step: the layers of the current maps
+  HIP_TRY(hipSetDevice(E->device));
+  if (E->stale) HIP_TRY(launch_dist(E, st));  // as mc_sg_step: the layers of the current maps
   E->stale = false;
   auto at = [](auto* p, int64_t off) { return reinterpret_cast<decltype(p)>(reinterpret_cast<uintptr_t>(p) + off); };
   if (E->s.dist) {
@@ -1748,7 +1687,7 @@ int mc_sg_step_many(void* env, const uint8_t* dev_actions, int64_t actions_strid
                                         at(dev_reward, k * reward_stride), at(dev_done, k * done_stride), st);
       if (he != hipSuccess) {  // steps 0..k-1 are enqueued: the env has advanced k steps
         E->stale = true;       // (a step kernel without its transform leaves the layer behind the maps)
-        return sg_fail(MC_EHIP, "mc_sg_step_many: step %d of %d failed after %d steps were enqueued: %s", (int)k,
+        return fail(MC_EHIP, "mc_sg_step_many: step %d of %d failed after %d steps were enqueued: %s", (int)k,
                        (int)num_steps, (int)k, hipGetErrorString(he));
       }
     }
@@ -1763,7 +1702,7 @@ int mc_sg_step_many(void* env, const uint8_t* dev_actions, int64_t actions_strid
   for (int64_t i = 0; i < chunks; ++i) {
     mc::FuseChunk c;
     if (!mc::fuse_chunk(num_steps, E->fuse_steps, i, stride, &c))
-      return sg_fail(MC_EINVAL, "mc_sg_step_many: chunk %lld of %lld", (long long)i, (long long)chunks);
+      return fail(MC_EINVAL, "mc_sg_step_many: chunk %lld of %lld", (long long)i, (long long)chunks);
     mcs::SgLoopArgs a;
     a.s = E->s;
     a.actions = at(dev_actions, c.off[mc::FUSE_ACTIONS]);
@@ -1779,31 +1718,28 @@ int mc_sg_step_many(void* env, const uint8_t* dev_actions, int64_t actions_strid
     const hipError_t he = hipGetLastError();
     if (he != hipSuccess) {  // the launches before it are enqueued: the env has advanced c.first steps
       E->stale = true;       // their maps have no transform yet: the next call runs it
-      return sg_fail(MC_EHIP,
+      return fail(MC_EHIP,
                      "mc_sg_step_many: step %lld of %d failed after %lld steps were enqueued: launch of %d steps: %s",
                      (long long)c.first, (int)num_steps, (long long)c.first, (int)c.count, hipGetErrorString(he));
     }
     ++E->step_launches;
     E->stale = true;
   }
-  SG_TRY(launch_dist(E, st));
+  HIP_TRY(launch_dist(E, st));
   E->stale = false;
   return MC_OK;
 }
 
 int64_t mc_sg_launches(void* env, int32_t which) {
   SgEnv* E = as_sg(env);
-  if (!E) return sg_fail(MC_EINVAL, "mc_sg_launches: null env");
-  if (which != 0 && which != 1) return sg_fail(MC_EINVAL, "mc_sg_launches: unknown counter %d", (int)which);
+  if (!E) return fail(MC_EINVAL, "mc_sg_launches: null env");
+  if (which != 0 && which != 1) return fail(MC_EINVAL, "mc_sg_launches: unknown counter %d", (int)which);
   return which == 0 ? E->step_launches : E->dist_launches;
 }
 
 const char* mc_sg_kernel_variant(void* env) {
   SgEnv* E = as_sg(env);
-  if (!E) {
-    sg_fail(MC_EINVAL, "mc_sg_kernel_variant: null env");
-    return "";
-  }
+  if (!E) return mc::fail_str(MC_EINVAL, "mc_sg_kernel_variant: null env");
   thread_local std::string name;
   const SgKernel& k = *E->step;
   name = k.name;
@@ -1827,35 +1763,35 @@ const char* mc_sg_kernel_name(int32_t index) {
 
 int64_t mc_sg_field_bytes(void* env, int32_t f) {
   SgEnv* E = as_sg(env);
-  if (!E) return sg_fail(MC_EINVAL, "mc_sg_field_bytes: null env");
+  if (!E) return fail(MC_EINVAL, "mc_sg_field_bytes: null env");
   SgField d = sg_field(E, f);
-  if (!d.ptr) return sg_fail(MC_EINVAL, "unknown state field %d", f);
+  if (!d.ptr) return fail(MC_EINVAL, "unknown state field %d", f);
   return d.bytes;
 }
 
 int mc_sg_get_state(void* env, int32_t f, void* dev_dst, int64_t bytes, void* stream) {
   SgEnv* E = as_sg(env);
-  if (!E || !dev_dst) return sg_fail(MC_EINVAL, "mc_sg_get_state: null argument");
+  if (!E || !dev_dst) return fail(MC_EINVAL, "mc_sg_get_state: null argument");
   SgField d = sg_field(E, f);
-  if (!d.ptr) return sg_fail(MC_EINVAL, "unknown state field %d", f);
-  if (bytes != d.bytes) return sg_fail(MC_EINVAL, "field %d is %lld bytes, got %lld", f, (long long)d.bytes, (long long)bytes);
-  SG_TRY(hipSetDevice(E->device));
-  SG_TRY(hipMemcpyAsync(dev_dst, d.ptr, (size_t)bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  if (!d.ptr) return fail(MC_EINVAL, "unknown state field %d", f);
+  if (bytes != d.bytes) return fail(MC_EINVAL, "field %d is %lld bytes, got %lld", f, (long long)d.bytes, (long long)bytes);
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(hipMemcpyAsync(dev_dst, d.ptr, (size_t)bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return MC_OK;
 }
 
 int mc_sg_set_state(void* env, int32_t f, const void* dev_src, int64_t bytes, void* stream) {
   SgEnv* E = as_sg(env);
-  if (!E || !dev_src) return sg_fail(MC_EINVAL, "mc_sg_set_state: null argument");
+  if (!E || !dev_src) return fail(MC_EINVAL, "mc_sg_set_state: null argument");
   SgField d = sg_field(E, f);
-  if (!d.ptr) return sg_fail(MC_EINVAL, "unknown state field %d", f);
-  if (f == MC_SG_FIELD_EP_PC || f == MC_SG_FIELD_EP_LEN) return sg_fail(MC_EINVAL, "field %d is read-only", f);
-  if (bytes != d.bytes) return sg_fail(MC_EINVAL, "field %d is %lld bytes, got %lld", f, (long long)d.bytes, (long long)bytes);
+  if (!d.ptr) return fail(MC_EINVAL, "unknown state field %d", f);
+  if (f == MC_SG_FIELD_EP_PC || f == MC_SG_FIELD_EP_LEN) return fail(MC_EINVAL, "field %d is read-only", f);
+  if (bytes != d.bytes) return fail(MC_EINVAL, "field %d is %lld bytes, got %lld", f, (long long)d.bytes, (long long)bytes);
   hipStream_t st = (hipStream_t)stream;
-  SG_TRY(hipSetDevice(E->device));
-  SG_TRY(hipMemcpyAsync(d.ptr, dev_src, (size_t)bytes, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipSetDevice(E->device));
+  HIP_TRY(hipMemcpyAsync(d.ptr, dev_src, (size_t)bytes, hipMemcpyDeviceToDevice, st));
   if (f == MC_SG_FIELD_GRID_NEG || f == MC_SG_FIELD_GRID_POS || f == MC_SG_FIELD_NUMPOS) E->grids_set = true;
-  SG_TRY(hipMemsetAsync(E->s.full, 1, (size_t)E->s.B, st));
+  HIP_TRY(hipMemsetAsync(E->s.full, 1, (size_t)E->s.B, st));
   E->stale = true;
   return MC_OK;
 }
@@ -1863,14 +1799,14 @@ int mc_sg_set_state(void* env, int32_t f, const void* dev_src, int64_t bytes, vo
 int mc_sg_copy_envs(void* dst, void* src, const int32_t* dev_src, void* stream) {
   SgEnv* D = as_sg(dst);
   SgEnv* S = as_sg(src);
-  if (!D || !S || !dev_src) return sg_fail(MC_EINVAL, "mc_sg_copy_envs: null argument");
+  if (!D || !S || !dev_src) return fail(MC_EINVAL, "mc_sg_copy_envs: null argument");
   const mcs::SState& d = D->s;
   const mcs::SState& s = S->s;
   if (S != D) {
     if (S->device != D->device)
-      return sg_fail(MC_EINVAL, "mc_sg_copy_envs: handles on HIP devices %d and %d", D->device, S->device);
+      return fail(MC_EINVAL, "mc_sg_copy_envs: handles on HIP devices %d and %d", D->device, S->device);
 #define SG_SAME(what, a, b) \
-  if ((a) != (b)) return sg_fail(MC_EINVAL, "mc_sg_copy_envs: %s differs (%d vs %d)", what, (int)(a), (int)(b))
+  if ((a) != (b)) return fail(MC_EINVAL, "mc_sg_copy_envs: %s differs (%d vs %d)", what, (int)(a), (int)(b))
     SG_SAME("num_agents", d.N, s.N);
     SG_SAME("width", d.W, s.W);
     SG_SAME("length", d.L, s.L);
@@ -1897,24 +1833,24 @@ int mc_sg_copy_envs(void* dst, void* src, const int32_t* dev_src, void* stream) 
   t.add(s.ep_len, d.ep_len, 4);
   t.add(s.dist_M, d.dist_M, 4);
   t.add(s.full, d.full, 1);
-  SG_TRY(hipSetDevice(D->device));
-  SG_TRY(mc::launch_fork(t, dev_src, s.B, d.B, S == D, d.err, mcs::ERR_FORK, (hipStream_t)stream));
+  HIP_TRY(hipSetDevice(D->device));
+  HIP_TRY(mc::launch_fork(t, dev_src, s.B, d.B, S == D, d.err, mcs::ERR_FORK, (hipStream_t)stream));
   D->stale = D->stale || S->stale;  // never more transforms than the source would run
   return MC_OK;
 }
 
 int mc_sg_check(void* env, void* stream) {
   SgEnv* E = as_sg(env);
-  if (!E) return sg_fail(MC_EINVAL, "mc_sg_check: null env");
+  if (!E) return fail(MC_EINVAL, "mc_sg_check: null env");
   hipStream_t st = (hipStream_t)stream;
-  SG_TRY(hipSetDevice(E->device));
+  HIP_TRY(hipSetDevice(E->device));
   uint32_t err = 0;
-  SG_TRY(hipMemcpyAsync(&err, E->s.err, 4, hipMemcpyDeviceToHost, st));
-  SG_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpyAsync(&err, E->s.err, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   if (err) {
-    SG_TRY(hipMemsetAsync(E->s.err, 0, 4, st));
-    SG_TRY(hipStreamSynchronize(st));
-    return sg_fail(MC_EDEVICE,
+    HIP_TRY(hipMemsetAsync(E->s.err, 0, 4, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return fail(MC_EDEVICE,
                    "device error word 0x%x (4=placement 8=inject 16=motion_penalty KeyError 32=copy_envs index)", err);
   }
   return MC_OK;

@@ -11,7 +11,7 @@
 #include <cstdio>
 #include <vector>
 
-#include "mc_internal.h"
+#include "mc_beams.h"
 
 static int fails = 0;
 #define CHECK(c, ...)                 \
