@@ -145,7 +145,9 @@ enum {
   MC_FIELD_DJ_LISTED = 18,   /* int32 [1] (env, agent) paths the last step sent
                                 to the full-map BFS, LDS or HBM
                                 (mc_dijkstra_variant): nearest unexplored cell
-                                more than 24 steps away (read-only diagnostic) */
+                                more than 24 steps away; B * N where every
+                                path goes there, MARLCOV_DJ_FULL=1 (read-only
+                                diagnostic)                                 */
   /* dist_reward configs only:                                                 */
   MC_FIELD_DIST_CACHED = 19, /* int32 [1] of the maps the last POST listed, those
                                 the top-cell cache served without a full

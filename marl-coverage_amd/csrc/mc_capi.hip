@@ -259,6 +259,12 @@ int setup_dijkstra(Env* E) {
   if (mc::dev_alloc(E->allocs, E->dj_list, (size_t)s.B * s.N + 3) != MC_OK)
     return fail(MC_EHIP, "dijkstra_input state: %s", mc::g_last_error.c_str());
   E->dj_window = !mc::env_is_1("MARLCOV_DJ_FULL");  // parity tests: every item on the full map
+  if (!E->dj_window) {
+    // no list, no count protocol: every step sends all B * N items to the full-map
+    // kernel, and MC_FIELD_DJ_LISTED (count word 2, which no kernel then writes) says so
+    const uint32_t all = (uint32_t)((size_t)s.B * s.N);
+    HIP_TRY(hipMemcpy(E->dj_list + 2, &all, sizeof all, hipMemcpyHostToDevice));
+  }
   return MC_OK;
 }
 

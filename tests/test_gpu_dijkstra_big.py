@@ -8,7 +8,11 @@ maps and counters each step.
 The depth of a search is set by injecting maps explored within L1 distance D
 of each robot: the nearest unexplored cell is then D steps away (or farther,
 behind obstacles), the BFS runs D layers deep, and the window kernel lists
-every item with D > 24 for the full-map kernel.
+every item with D > 24 for the full-map kernel.  On these maps the geodesic
+distance is the L1 distance give or take a cell; that "farther" -- targets a
+few cells away behind a wall, corridors that wind for thousands of layers,
+tied ends and tied walks back -- is what test_gpu_dijkstra_mazes.py tests, on
+the authored mazes of dijkstra_maze_cases.py.
 """
 import os
 
